@@ -10,7 +10,11 @@ OpenWebText-shaped tokens, random-init weights (no network).  One "step" =
 one full optimizer step (forward, backward, gradient all-reduce over RCCL,
 fused AdamW).  Weak scaling: every rank processes 32 x 256 tokens per step.
 
-  python bench.py --gpus N --steps K --warmup W [--config {1..5}]
+  python bench.py --gpus N --steps K --warmup W [--config {1..5}] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds the
+wall-clock/epoch measurement (two more passes over ``--epoch_lines`` lines, one of them by a fresh
+model + Trainer).  ``--dump-outputs DIR`` writes what the last timed step computed (``dump_outputs``).
 
 With N > 1 and no torchrun environment (WORLD_SIZE unset) this process starts the N ranks itself:
 it runs ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1`` on this file
@@ -27,7 +31,7 @@ Under torchrun (``WORLD_SIZE`` set, as the driver launches it) the formed world 
   5  OPT-6.7B fp16 LoRA, 8-stage pipeline (--gpus 8)
 
 Prints ONE JSON line on rank 0.  `value` = whole-job steady-state tokens/s over the K timed
-steps; ``wall_clock_epoch_s`` = one full epoch over a 20k-line medium_openwebtext-shaped
+steps; ``wall_clock_epoch_s`` (``--full`` only, else null) = one full epoch over a 20k-line medium_openwebtext-shaped
 corpus (the reference's other metric, strong-scaled over the DP ranks) by a fresh model + Trainer,
 timed from its first step like the reference's [Training] phase (its construction, incl. the
 setup-time warm-up and graph capture, is reported as ``epoch.trainer_setup_s``; the same epoch on
@@ -82,10 +86,15 @@ def parse_args(argv=None):
                     help="fused = mift HIP kernels; torch = eager PyTorch ops on the same model (comparison)")
     ap.add_argument("--profile_dir", default=None, help="torch.profiler chrome trace of 3 steps")
     ap.add_argument("--epoch_lines", type=int, default=None,
-                    help="after the timed steps, run one full epoch over this many medium_openwebtext-shaped "
+                    help="with --full: after the timed steps, run one full epoch over this many medium_openwebtext-shaped "
                          "lines (README.md:66: ~20k) sharded over the DP ranks and report its wall clock "
                          "(the reference's [Training] sec metric, P1 and P2 alike: P2/summarize_opt_times.py:39-51); "
                          "default 20000, 0 skips it")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the wall-clock/epoch passes "
+                         "(--epoch_lines); off by default")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     a = ap.parse_args(argv)
     c = dict(CONFIGS[a.config])
     if a.model and a.model != c["model"]:  # a model override keeps that family's reference precision
@@ -117,6 +126,34 @@ def _free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss_sum, ntok, params, grad_norm, budget=DUMP_BUDGET_BYTES):
+    """What a caller of the timed path (``Trainer.train_step``) holds after the last timed step: the
+    step's returned summed token loss and token count, the trainable-parameter arena it updated in
+    place, and the step's gradient norm (the gradients themselves are zeroed by the optimizer).  One
+    ``<name>.npy`` each, float32 / float64; an arena over the byte budget is written as a fixed,
+    seeded sample of its elements (``lora_params_index.npy`` holds the sampled positions)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"ntok": np.asarray([float(ntok)], dtype=np.float64),
+              "grad_norm": np.asarray([float(grad_norm)], dtype=np.float64)}
+    if loss_sum is not None:  # a pipeline's first stage holds no loss
+        arrays["loss_sum"] = np.asarray([float(loss_sum)], dtype=np.float64)
+    p = params.detach().float().cpu().numpy().reshape(-1)
+    room = (budget - 4096) // 4
+    if p.size > room:
+        # float32 values + float64 positions: 12 bytes per sampled element
+        idx = np.sort(np.random.default_rng(20240229).choice(p.size, size=(budget - 4096) // 12, replace=False))
+        arrays["lora_params_index"] = idx.astype(np.float64)
+        p = p[idx]
+    arrays["lora_params"] = np.ascontiguousarray(p, dtype=np.float32)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(arrays)
 
 
 def launch(a):
@@ -241,7 +278,7 @@ def main():
     assert len(steps) >= total_steps
 
     def run(i):
-        tr.train_step(steps[i])
+        return tr.train_step(steps[i])
 
     for i in range(a.warmup):
         run(i)
@@ -253,8 +290,9 @@ def main():
     sync_every = int(os.environ.get("MIFT_BENCH_SYNC", "0"))  # diagnostics: host sync every k steps
     t0 = time.perf_counter()
     last = t0
+    last_out = None
     for i in range(a.warmup, total_steps):
-        run(i)
+        last_out = run(i)
         if not trace and ctx.rank == 0 and time.perf_counter() - last > 30.0:
             last = time.perf_counter()
             print(f"bench.py: step {i + 1 - a.warmup}/{a.steps} {last - t0:.1f}s", file=sys.stderr, flush=True)
@@ -276,6 +314,9 @@ def main():
     tokens_per_step = per_rank * a.seq_len * ctx.dp
     value = tokens_per_step / (ms / 1000.0)
     stats = tr.opt.stats()
+    if a.dump_outputs and ctx.rank == 0 and last_out is not None:
+        loss_sum, ntok = last_out
+        dump_outputs(a.dump_outputs, loss_sum, ntok, tr.arena.param, stats["grad_norm"])
     if a.profile_dir and ctx.rank == 0:
         from torch.profiler import profile, ProfilerActivity
         with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
@@ -287,7 +328,7 @@ def main():
         with open(os.path.join(a.profile_dir, "table.txt"), "w") as f:
             f.write(prof.key_averages().table(sort_by="cuda_time_total", row_limit=40))
     epoch_s, epoch_steps, warm_epoch_s, setup_s = None, None, None, None
-    if a.epoch_lines > 0:
+    if a.full and a.epoch_lines > 0:
         # wall-clock/epoch, the other half of the BASELINE metric (reference: max over ranks of
         # `[Training] x sec`, P1/summarize_medium_times.py:4-10) over a medium-shaped corpus,
         # strong-scaled over the DP ranks like the reference's fixed dataset at N nodes.
@@ -367,6 +408,7 @@ def main():
                        "model_override": a.model != base["model"],
                        "final_grad_norm": round(stats["grad_norm"], 4)},
             "wall_clock_epoch_s": epoch_s,
+            "full": bool(a.full),
             "epoch": {"lines": a.epoch_lines, "steps": epoch_steps, "global_batch": per_rank * ctx.dp,
                       "definition": "one pass over the medium-shaped corpus by a FRESH model + Trainer, timed "
                                     "from its first step, max over ranks (reference [Training] sec)",

@@ -94,9 +94,61 @@ def test_bench_config3_reports_epoch():
     assert bench.parse_args(["--config", "2"]).epoch_lines == 20000
     args = ["--gpus", "2", "--config", "3", "--pp", "2", "--model", "opt-tiny", "--precision", "fp32", "--seq_len",
             "32", "--accum", "4", "--device", "cpu", "--steps", "1", "--warmup", "0", "--epoch_lines", "16"]
-    out = _run(args)
+    out = _run(args + ["--full"])
     assert out.returncode == 0, out.stderr[-3000:]
     r = _json(out)
     assert r["wall_clock_epoch_s"] is not None and r["wall_clock_epoch_s"] > 0
     assert r["epoch"]["lines"] == 16 and r["epoch"]["steps"] == 4  # 16 lines / (1 x 4 per step)
     assert r["config"]["parallelism"].startswith("dp1xpp2")
+
+
+TINY1 = ["--gpus", "1", "--config", "1", "--model", "opt-tiny", "--precision", "fp32", "--seq_len", "32", "--accum", "4",
+         "--steps", "2", "--warmup", "1"]
+
+
+def test_bench_plain_run_skips_epoch_and_dumps_outputs(tmp_path):
+    """A plain run times its steps only (the epoch passes are behind --full, whatever --epoch_lines says) and
+    --dump-outputs writes what the last timed step computed; the same arguments give the same arrays."""
+    import numpy as np
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        out = _run(TINY1 + ["--epoch_lines", "16", "--dump-outputs", str(d)])
+        assert out.returncode == 0, out.stderr[-3000:]
+        r = _json(out)
+        assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0
+        assert r["full"] is False and r["wall_clock_epoch_s"] is None and r["epoch"] is None
+        arrs = {f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+        assert set(arrs) == {"loss_sum", "ntok", "grad_norm", "lora_params"}
+        assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in arrs.values())
+        assert sum(v.nbytes for v in arrs.values()) <= 64 << 20
+        assert arrs["ntok"][0] == 4 * 31 and arrs["loss_sum"][0] > 0 and arrs["lora_params"].any()
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_bench_dump_samples_large_outputs(tmp_path):
+    """An arena over the byte budget is written as a fixed sample: same positions every time, within budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    p = torch.arange(5000, dtype=torch.float32)
+    for name in ("a", "b"):
+        names = bench.dump_outputs(str(tmp_path / name), torch.tensor(3.0), 7, p, 0.5, budget=4096 + 1200)
+        assert names == ["grad_norm", "lora_params", "lora_params_index", "loss_sum", "ntok"]
+    a = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in names}
+    b = {n: np.load(str(tmp_path / "b" / (n + ".npy"))) for n in names}
+    assert all(np.array_equal(a[n], b[n]) for n in names)
+    assert a["lora_params"].size == 100 and sum(v.nbytes for v in a.values()) <= 4096 + 1200
+    assert np.array_equal(a["lora_params"], a["lora_params_index"].astype(np.float32))  # p[i] == i
+    assert np.all(np.diff(a["lora_params_index"]) > 0)
+
+
+def test_bench_full_is_off_by_default():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert a.full is True and a.steps == 3 and a.warmup == 1 and a.dump_outputs is None

@@ -10,5 +10,5 @@ bash tools/gpu_job.sh \
   "p1_medium:300:python scripts/finetune_lora_distilgpt2.py --dataset medium --logdir $O/p1_logs --out_root $O/p1_out --logging_steps 100 --step_log none && python scripts/summarize_medium_times.py $O/p1_logs" \
   "tiny_bert:300:python labs/tiny/train_tiny.py --subset 2000 --epochs 1 --batch 8 --out $O/tiny_out --no_tb" \
   "gen_probe:200:python scripts/gen_probe.py --repeat 3" \
-  "opt27b:400:python bench.py --model facebook/opt-2.7b --micro_batch 48 --steps 3 --warmup 1" \
-  "opt67b:500:python bench.py --model facebook/opt-6.7b --micro_batch 24 --steps 3 --warmup 1"
+  "opt27b:400:python bench.py --full --model facebook/opt-2.7b --micro_batch 48 --steps 3 --warmup 1" \
+  "opt67b:500:python bench.py --full --model facebook/opt-6.7b --micro_batch 24 --steps 3 --warmup 1"
