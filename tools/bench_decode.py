@@ -46,10 +46,6 @@ def main():
         col.zero_()
         K.decode_tail(logits, V, done, ids, out, col, pos, t, 0, 50256, 50256)
 
-    for nth in ("256", "512", "1024"):
-        os.environ["MIFT_TAIL_NTH"] = nth
-        rec(f"decode_tail(+col reset) {nth} threads", tail)
-    os.environ.pop("MIFT_TAIL_NTH")
     rec("decode_tail(+col reset)", tail)
     # the tail's last steps alone: one row's argmax over 64 columns (bookkeeping-bound)
     rec("decode_tail V=64 (bookkeeping only)", lambda: (col.zero_(), K.decode_tail(logits, 64, done, ids, out, col, pos,
@@ -69,8 +65,7 @@ def main():
         w = (torch.randn(N, Kd, device=dev) / Kd ** 0.5).to(dt)
         rec(f"gemm {name} {B}x{N}x{Kd}", lambda: K.gemm(xa, w))
         rec(f"gemm {name} tile4", lambda: K.gemm(xa, w, tile=4))
-    # epilogue-operand prefetch A/B (MIFT_SKINNY_PF, read per call) on the decode epilogues: bias (+gelu)
-    # for the LN-prologue GEMMs, bias + residual for c_proj / fc2 (K split 3)
+    # the decode epilogues: bias (+gelu) for the LN-prologue GEMMs, bias + residual for c_proj / fc2 (K split 3)
     res = torch.randn(B, d, device=dev).to(dt)
     cases = []
     for name, N, Kd, act in (("c_attn", 3 * d, d, 0), ("c_fc", 4 * d, d, 1)):
@@ -83,18 +78,7 @@ def main():
         bias = torch.randn(d, device=dev).to(dt)
         cases.append((f"gemm {name} +bias+res", lambda xa=xa, w=w, bias=bias: K.gemm(xa, w, bias, residual=res)))
     for name, fn in cases:
-        ts = {"0": [], "1": []}
-        outs = {}
-        for _ in range(3):
-            for pf in ("0", "1"):
-                os.environ["MIFT_SKINNY_PF"] = pf
-                ts[pf].append(timeit(fn))
-                outs[pf] = fn()
-        os.environ.pop("MIFT_SKINNY_PF")
-        same = torch.equal(outs["0"][0] if isinstance(outs["0"], tuple) else outs["0"],
-                           outs["1"][0] if isinstance(outs["1"], tuple) else outs["1"])
-        row = {"name": name, "pf0_us": round(min(ts["0"]) * 1e3, 2), "pf1_us": round(min(ts["1"]) * 1e3, 2),
-               "bit_identical": bool(same)}
+        row = {"name": name, "us": round(min(timeit(fn) for _ in range(3)) * 1e3, 2)}
         print(json.dumps(row), flush=True)
         rows.append(row)
     if a.json:

@@ -1,6 +1,5 @@
-"""LM-head dgrad (EPI 2) with and without its per-column-group accumulator rescale (MIFT_LM_DBG bit 3:
-timing only, wrong numbers) and over the split-K count (MIFT_LM_SPLIT), distilgpt2 and OPT-2.7B shapes,
-interleaved rounds in one process."""
+"""LM-head dgrad (EPI 2: split-K kernel + slab reduction) at the distilgpt2 and OPT-2.7B shapes, best of
+3 rounds in one process."""
 import json
 import os
 import statistics
@@ -35,18 +34,8 @@ def main():
         lab = torch.randint(0, V, (M,), device="cuda")
         E, stats, lse, loss, zlab = K.lmhead_fwd(a, w, lab, V)[:5]
         g = torch.ones(1, device="cuda")
-        res = {}
-        arms = {"default": {}, "no_rescale": {"MIFT_LM_DBG": "8"}}
-        for sp in (4, 6, 7, 8, 10, 12):
-            arms[f"split{sp}"] = {"MIFT_LM_SPLIT": str(sp)}
-        for _ in range(3):
-            for name, env in arms.items():
-                os.environ.update(env)
-                res.setdefault(name, []).append(timeit(lambda: K.lmhead_dgrad(E, wt, w, lab, V, stats, lse, g)))
-                for k in env:
-                    os.environ.pop(k, None)
-        print(json.dumps({"M": M, "d": d, "V": V, **{k + "_us": round(min(v) * 1e3, 1) for k, v in res.items()}}),
-              flush=True)
+        ts = [timeit(lambda: K.lmhead_dgrad(E, wt, w, lab, V, stats, lse, g)) for _ in range(3)]
+        print(json.dumps({"M": M, "d": d, "V": V, "us": round(min(ts) * 1e3, 1)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
-"""Persistent vs one-tile fused LM-head forward (MIFT_LM_PERSIST) and the tile raster (MIFT_GEMM_GROUP),
-at the distilgpt2 and OPT-2.7B shapes: arms interleaved in one process (guide §5.4 rule 24), median of
+"""Persistent vs one-tile fused LM-head forward (MIFT_LM_PERSIST) at the distilgpt2 and OPT-2.7B
+shapes: arms interleaved in one process (guide §5.4 rule 24), median of
 5 rounds x 10 launches, random data; every arm's outputs compared bitwise with the one-tile kernel's."""
 import json
 import os
@@ -11,18 +11,11 @@ import torch  # noqa: E402
 
 from mift.ops import kernels as K  # noqa: E402
 
-ARMS = [("onetile", {"MIFT_LM_PERSIST": "0", "MIFT_LM_GROUP": "0"}),
-        ("onetile_auto", {"MIFT_LM_PERSIST": "0"}),
-        ("persist_g0", {"MIFT_LM_PERSIST": "1", "MIFT_LM_GROUP": "0"}),
-        ("persist_auto", {"MIFT_LM_PERSIST": "1"}),
-        ("persist_g4", {"MIFT_LM_PERSIST": "1", "MIFT_LM_GROUP": "4"}),
-        ("persist_g8", {"MIFT_LM_PERSIST": "1", "MIFT_LM_GROUP": "8"}),
-        ("persist_nostore", {"MIFT_LM_PERSIST": "1", "MIFT_LM_DBG": "1"})]
+ARMS = [("onetile", {"MIFT_LM_PERSIST": "0"}), ("persist", {"MIFT_LM_PERSIST": "1"})]
 
 
 def setenv(env):
-    for k in ("MIFT_LM_PERSIST", "MIFT_GEMM_GROUP", "MIFT_LM_GROUP", "MIFT_LM_DBG"):
-        os.environ.pop(k, None)
+    os.environ.pop("MIFT_LM_PERSIST", None)
     os.environ.update(env)
 
 
@@ -55,11 +48,7 @@ for name, M, d, V, dt in [("distilgpt2", 8192, 768, 50257, torch.bfloat16),
     for arm, _ in ARMS:
         row[arm + "_us"] = round(statistics.median(ts[arm]), 1)
         if arm != "onetile":
-            ref = outs["onetile"]
-            if arm == "persist_nostore":  # E not written: compare the statistics / loss only
-                row[arm + "_same"] = all(torch.equal(p, q) for p, q in zip(outs[arm][1:], ref[1:]))
-            else:
-                row[arm + "_same"] = all(torch.equal(p, q) for p, q in zip(outs[arm], ref))
+            row[arm + "_same"] = all(torch.equal(p, q) for p, q in zip(outs[arm], outs["onetile"]))
     fl = 2.0 * M * Vp * d
-    row["persist_auto_tflops"] = round(fl / row["persist_auto_us"] / 1e6, 1)
+    row["persist_tflops"] = round(fl / row["persist_us"] / 1e6, 1)
     print(json.dumps(row), flush=True)

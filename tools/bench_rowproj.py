@@ -59,22 +59,10 @@ def main():
             row["mask_proj_us"] = round(t * 1e3, 1)
             t = timeit(lambda: K.mask_scale(x, 0.1, 7))
             row["mask_scale_us"] = round(t * 1e3, 1)
-            if D in (768, 1024):  # the MFMA 16-row form runs by default there; the row kernels for A/B
-                os.environ["MIFT_ROWPROJ_V"] = "1"
-                t = timeit(lambda: K.layer_norm_fwd_proj(x, lw, lb, 1e-5, w32, r, 1.0, 0.05, 7))
-                row["ln_fwd_proj_rowkernel_us"] = round(t * 1e3, 1)
-                t = timeit(lambda: K.mask_proj(x, 0.1, 7, w32, r, 1.0))
-                row["mask_proj_rowkernel_us"] = round(t * 1e3, 1)
-                os.environ.pop("MIFT_ROWPROJ_V")
         t = timeit(lambda: K.lora_proj(x, w32, 1.0, 0.05, 7))
         row["lora_proj_p_us"] = round(t * 1e3, 1)
         t = timeit(lambda: K.lora_proj(x, w32, 1.0, 0.0, 0))
         row["lora_proj_us"] = round(t * 1e3, 1)
-        if D in (768, 1024, 2304):  # rowproj MFMA form by default; lora_proj's own kernel for A/B
-            os.environ["MIFT_ROWPROJ_V"] = "1"
-            t1 = timeit(lambda: K.lora_proj(x, w32, 1.0, 0.05, 7))
-            row["lora_proj_p_oldkernel_us"] = round(t1 * 1e3, 1)
-            os.environ.pop("MIFT_ROWPROJ_V")
         row["lora_proj_GBps"] = round(gb / (t * 1e-3), 0)
         t = timeit(lambda: torch.mm(x, w32.t()))
         row["torch_mm_us"] = round(t * 1e3, 1)

@@ -4,7 +4,7 @@ separate passes they replace in an OPT training step (fp16, micro-batch 12 x 512
   fwd  LN + q/k/v (or fc1) input projection:  layer_norm_fwd_proj   vs  layer_norm_fwd + lora_proj
   bwd  LN-bwd + residual-dropout-bwd + dT:     ln_bwd_mask_proj      vs  layer_norm_bwd + mask_scale + lora_proj
   bwd  residual-dropout-bwd + dT:              mask_proj             vs  mask_scale + lora_proj
-  plain projection (out_proj input):           lora_proj (MODE 2)    vs  lora_proj's own kernel (MIFT_ROWPROJ_V=1)
+  plain projection (out_proj input):           lora_proj (MODE 2)
 
   python tools/bench_rowproj_opt.py [--json out.json]
 """
@@ -56,10 +56,6 @@ def main():
         r["mask_proj_us"] = t(lambda: K.mask_proj(dy, 0.1, 7, pw, rank, 1.0))
         r["mask_scale+lora_proj_us"] = t(lambda: (K.mask_scale(dy, 0.1, 7), K.lora_proj(dy, pw, 1.0, 0.0, 0, rows=rank)))
         r["lora_proj_mfma_us"] = t(lambda: K.lora_proj(x, pw, 1.0, 0.05, 7, rows=rank))
-        os.environ["MIFT_ROWPROJ_V"] = "1"
-        r["lora_proj_own_us"] = t(lambda: K.lora_proj(x, pw, 1.0, 0.05, 7, rows=rank))
-        r["ln_fwd_proj_rowkernel_us"] = t(lambda: K.layer_norm_fwd_proj(x, lw, lb, 1e-5, pw, rank, 1.0, 0.05, 7))
-        os.environ.pop("MIFT_ROWPROJ_V")
         r["hbm_floor_ln_bwd_mask_proj_us"] = round(5 * M * D * 2 / 6.0e12 * 1e6, 1)  # dy, x, dres in; dh, y out
         print(json.dumps(r), flush=True)
         rows.append(r)
@@ -71,9 +67,6 @@ def main():
         pw[:24] = (torch.randn(24, 7680, device=dev) * 0.02).to(dt)
         r = {"M": m, "D": 7680, "rows": 24}
         r["lora_proj_mfma_us"] = round(timeit(lambda: K.lora_proj(g, pw, 1.0, 0.0, 0, rows=24)) * 1e3, 1)
-        os.environ["MIFT_ROWPROJ_V"] = "1"
-        r["lora_proj_own_us"] = round(timeit(lambda: K.lora_proj(g, pw, 1.0, 0.0, 0, rows=24)) * 1e3, 1)
-        os.environ.pop("MIFT_ROWPROJ_V")
         r["hbm_floor_us"] = round(m * 7680 * 2 / 6.0e12 * 1e6, 1)
         print(json.dumps(r), flush=True)
         rows.append(r)

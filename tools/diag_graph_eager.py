@@ -74,9 +74,6 @@ def main():
             "eager2": run(a.model, a.precision, a.steps, False, True),
             "graph": run(a.model, a.precision, a.steps, True, True),
             "graph_nowarm": run(a.model, a.precision, a.steps, True, False)}
-    if a.precision == "fp16":
-        os.environ["MIFT_DIAG_NOREBIND"] = "1"
-        runs["graph_norebind"] = run(a.model, a.precision, a.steps, True, True)
     base = runs["eager"]
     for name, r in runs.items():
         rec = {"run": name, "loss": r["loss"], "gn": r["gn"], "found_inf": r["inf"]}

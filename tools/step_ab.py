@@ -6,7 +6,7 @@ hides few-percent kernel changes.  Here two (or more) trainers are built in ONE 
 under its own environment (kernel knobs are read when the step's graph is captured), and
 their steps are timed in interleaved blocks; the medians are compared.
 
-  python tools/step_ab.py "MIFT_GEMM_GROUP=0" "MIFT_GEMM_GROUP=4" [--blocks 6 --steps 10]
+  python tools/step_ab.py "MIFT_GEMM_T10=0" "MIFT_GEMM_T10=1" [--blocks 6 --steps 10]
 (AB_LORA_P=x / AB_MODEL_PDROP=x: diagnostic arms with other dropout rates)
 """
 import argparse

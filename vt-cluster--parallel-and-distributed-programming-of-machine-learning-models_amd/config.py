@@ -20,13 +20,13 @@ Reference: P2 loads a DeepSpeed JSON (``--ds_cfg``,
   halves: half-layer units),
   ``pp_schedule`` (1f1b), ``micro_batch`` (GPU micro-batch regrouping: an int, or "auto" = the
   pipeline planner ``mift.parallel.plan.choose_micro_batch``), ``virtual_stages`` (interleaved 1F1B
-  chunks per pipeline rank: an int, or "auto" = chosen with the micro-batch), ``side_stream``
-  (LoRA weight grads on a second stream), ``comm_timeout_s`` (collective watchdog),
+  chunks per pipeline rank: an int, or "auto" = chosen with the micro-batch),
+  ``comm_timeout_s`` (collective watchdog),
   ``consistency_every`` (replica checksum period), ``max_inflight_steps`` (host run-ahead bound);
 * anything else is an error unless ``mift.strict`` is false (then a warning).
 
 ``MiftConfig.apply_env()`` exports the process-wide toggles (``MIFT_KERNELS``, ``MIFT_GRAPH``,
-``MIFT_LMHEAD``, ``MIFT_SIDE_STREAM``, ``MIFT_COMM_TIMEOUT``) the runtime reads.
+``MIFT_LMHEAD``, ``MIFT_COMM_TIMEOUT``) the runtime reads.
 """
 import json
 import os
@@ -50,9 +50,10 @@ _NO_EFFECT = {
     "activation_checkpointing.contiguous_memory_optimization": "PyTorch caching allocator",
     "steps_per_print": "logging_steps / --log_every control logging",
     "wall_clock_breakdown": "phase timers are always on (timing_rank*.log)",
+    "mift.side_stream": "the second stream for LoRA weight grads was removed (measured slower); they run inline",
 }
 _MIFT_KEYS = {"kernels", "graph", "lmhead", "bucket_mb", "pp_partition", "pp_schedule", "micro_batch", "virtual_stages",
-              "side_stream",
+              "side_stream",  # accepted for old configs, reported as having no effect (_NO_EFFECT)
               "comm_timeout_s", "consistency_every", "max_inflight_steps", "strict"}
 
 
@@ -82,7 +83,6 @@ class MiftConfig:
     pp_schedule: str = "1f1b"
     micro_batch: object = 0          # int, or "auto" (planner); 0 = the DeepSpeed micro-batch as is
     virtual_stages: object = None    # int, or "auto"; None = the app's default
-    side_stream: Optional[bool] = None
     comm_timeout_s: Optional[int] = None
     consistency_every: int = 0
     max_inflight_steps: int = 2
@@ -148,7 +148,6 @@ class MiftConfig:
         c.micro_batch = "auto" if str(mb).lower() == "auto" else int(mb)
         vs = m.get("virtual_stages")
         c.virtual_stages = None if vs is None else ("auto" if str(vs).lower() == "auto" else int(vs))
-        c.side_stream = m.get("side_stream")
         c.comm_timeout_s = m.get("comm_timeout_s")
         c.consistency_every = int(m.get("consistency_every", 0))
         c.max_inflight_steps = int(m.get("max_inflight_steps", 2))
@@ -173,8 +172,6 @@ class MiftConfig:
         os.environ.setdefault("MIFT_KERNELS", "1" if self.kernels else "0")
         os.environ.setdefault("MIFT_GRAPH", self.graph)
         os.environ.setdefault("MIFT_LMHEAD", self.lmhead)
-        if self.side_stream is not None:
-            os.environ.setdefault("MIFT_SIDE_STREAM", "1" if self.side_stream else "0")
         if self.comm_timeout_s:
             os.environ.setdefault("MIFT_COMM_TIMEOUT", str(int(self.comm_timeout_s)))
 

@@ -49,6 +49,14 @@ __device__ __forceinline__ uint64_t mift_seed(uint64_t s, const int64_t* sstep) 
 // host: the device micro-step counter bound by mift._C.set_seed_step (nullptr = eager)
 const int64_t* mift_seed_step();
 
+// host: the one way native code reads a MIFT_* switch (docs/KNOBS.md lists them): the integer value,
+// or `dflt` when unset.  Read per call, never cached, so a test or an A/B tool may flip a switch
+// in-process; a launch recorded into a hipGraph keeps the value read at capture time.
+inline int mift_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 // host: deterministic reductions — no float atomics in any gradient reduction, so a
 // step's results are bit-identical run to run.  On by default; MIFT_DETERMINISTIC=0 opts out.
 inline bool mift_deterministic() {

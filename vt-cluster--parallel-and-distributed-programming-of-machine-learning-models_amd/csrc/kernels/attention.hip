@@ -185,16 +185,11 @@ MIFT_HD void load_reg_frags(vec8<T>* f, const T* src, int64_t ld, int row, int n
 // (dK/dV), re-read once per tile.  Blocks are dealt round-robin over the 8 XCDs (b and b + 8 share
 // one), so consecutive block ids — one head's tiles — sat on 8 different L2s and every re-read went to
 // the Infinity Cache.  The bijective remap (gemm.hip, guide T1) gives each XCD a contiguous run of
-// block ids: a head's tiles run on one XCD and re-read its L2.  MIFT_ATTN_XCD=0: off (A/B).
-MIFT_HD int attn_block_id(int xcd_remap) {
+// block ids: a head's tiles run on one XCD and re-read its L2.
+MIFT_HD int attn_block_id() {
   const int b = blockIdx.x;
-  if (!xcd_remap) return b;
   const int n = gridDim.x, q = n / 8, r = n % 8, xcd = b % 8, loc = b / 8;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-inline int attn_xcd_env() {
-  const char* e = getenv("MIFT_ATTN_XCD");
-  return e ? atoi(e) : 1;
 }
 
 MIFT_HD bool drop_keep(uint64_t seed, uint32_t thr, int64_t bh, int S, int q, int k) {
@@ -220,8 +215,7 @@ template <typename T, int HD, int QG, bool OT = true>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                        float* __restrict__ lse, const int* __restrict__ kv_len,
                                                        int B, int S, int H, float scale, uint64_t seed,
-                                                       const int64_t* __restrict__ sstep, uint32_t thr, float inv_keep,
-                                                       int xcd) {
+                                                       const int64_t* __restrict__ sstep, uint32_t thr, float inv_keep) {
   seed = mift_seed(seed, sstep);
   using G = Geo<HD>;
   constexpr int BQB = BQ * QG;  // queries per block
@@ -232,7 +226,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar branches on it
   const int g = lane >> 4, qc = lane & 15;
   const int nqt = (S + BQB - 1) / BQB;
-  const int bid = attn_block_id(xcd);
+  const int bid = attn_block_id();
   const int qt = nqt - 1 - (bid % nqt);  // heavy (late) query tiles first
   const int bh = bid / nqt;
   const int b = bh / H, h = bh % H;
@@ -446,9 +440,8 @@ MIFT_HD void seq_block(const SeqSplit& sp, int ng, int& bh, int& g0, int& g1) {
 inline SeqSplit seq_split_plan(int BH, int S, int cus, int& blocks) {
   SeqSplit sp{BH, 0};
   blocks = BH;
-  const char* e = getenv("MIFT_ATTN_SPLIT");
   const int ng = (S + 15) / 16;
-  if ((e && atoi(e) == 0) || BH <= cus || BH >= 2 * cus || ng < 4) return sp;
+  if (mift_env_int("MIFT_ATTN_SPLIT", 1) == 0 || BH <= cus || BH >= 2 * cus || ng < 4) return sp;
   const int k = 2 * cus - BH;  // heads split in two
   sp.nfull = BH - k;
   long tot = 0;
@@ -484,8 +477,7 @@ inline SeqSplit seq_split_plan_kv(int BH, int S, int cus, int& blocks) {
 // MIFT_ATTN_SEQ: 0 = tiled kernels only, 1 = whole-sequence kernels when they fit and there are
 // >= 256 heads to fill the chip (default), 2 = whenever they fit (tests, A/B); read per call
 int attn_seq_mode() {
-  const char* e = getenv("MIFT_ATTN_SEQ");
-  return e ? atoi(e) : 1;
+  return mift_env_int("MIFT_ATTN_SEQ", 1);
 }
 
 template <typename T, int HD, int NW, bool OT = true>  // OT: see attn_fwd_kernel
@@ -715,7 +707,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ 
                                                           float* __restrict__ Dv, T* __restrict__ dqkv,
                                                           const int* __restrict__ kv_len, int B, int S, int H,
                                                           float scale, uint64_t seed, const int64_t* __restrict__ sstep, uint32_t thr,
-                                                          float inv_keep, int xcd) {
+                                                          float inv_keep) {
   seed = mift_seed(seed, sstep);
   using G = Geo<HD>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -726,7 +718,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar branches on it
   const int g = lane >> 4, qc = lane & 15;
   const int nqt = (S + BQ - 1) / BQ;
-  const int bid = attn_block_id(xcd);
+  const int bid = attn_block_id();
   const int qt = nqt - 1 - (bid % nqt);
   const int bh = bid / nqt;
   const int b = bh / H, h = bh % H;
@@ -835,8 +827,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(const T* __rest
                                                             const float* __restrict__ lse, const float* __restrict__ Dv,
                                                             T* __restrict__ dqkv, const int* __restrict__ kv_len,
                                                             int B, int S, int H, float scale, uint64_t seed,
-                                                            const int64_t* __restrict__ sstep, uint32_t thr, float inv_keep,
-                                                            int xcd) {
+                                                            const int64_t* __restrict__ sstep, uint32_t thr, float inv_keep) {
   seed = mift_seed(seed, sstep);
   using G = Geo<HD>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -850,7 +841,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(const T* __rest
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar branches on it
   const int g = lane >> 4, kc = lane & 15;
   const int nkt = (S + BKV - 1) / BKV;
-  const int bid = attn_block_id(xcd);
+  const int bid = attn_block_id();
   const int kt = bid % nkt;
   const int bh = bid / nkt;
   const int b = bh / H, h = bh % H;
@@ -1330,10 +1321,9 @@ template <typename T, int HD>
 void fwd_launch(const at::Tensor& qkv, at::Tensor& o, at::Tensor& lse, const int* kvl, int B, int S, int H, float scale,
                 uint64_t seed, uint32_t thr, float inv_keep, hipStream_t st, uint16_t* dmask) {
   using G = Geo<HD>;
-  // query groups per wave (MIFT_ATTN_QG=1|2).  QG = 2 halves LDS bytes per MFMA but needs
-  // 193 VGPRs (2 waves/SIMD vs 3) and measured slower on MI355X (tools/bench_attn.py: OPT-2.7B
-  // fwd 75.2 vs 69.9 us, distilgpt2 41.0 vs 32.1 us, OPT-6.7B 243 vs 152 us): default 1
-  static const int qg = [] { const char* e = getenv("MIFT_ATTN_QG"); return e ? atoi(e) : 1; }();
+  // one query group per wave: QG = 2 halves LDS bytes per MFMA but needs 193 VGPRs (2 waves/SIMD vs 3)
+  // and measured slower on MI355X (OPT-2.7B fwd 75.2 vs 69.9 us, distilgpt2 41.0 vs 32.1 us, OPT-6.7B
+  // 243 vs 152 us)
   const int seq_env = attn_seq_mode();
   const int smem = G::ROW_BYTES + G::TR_BYTES;
   // whole-sequence kernel when K and V of one head fit in LDS next to another block's (two
@@ -1344,8 +1334,7 @@ void fwd_launch(const at::Tensor& qkv, at::Tensor& o, at::Tensor& lse, const int
   // transposed-output P·V (read per call: A/B): on for the whole-sequence kernel (distilgpt2 fwd 23.3 ->
   // 22.8 us), off for the tiled one (OPT-2.7B 49.2 vs 49.9 us, OPT-6.7B 115.9 vs 118.5;
   // profiles/r5/bench_attn_ot_xcd.jsonl)
-  const char* ote = getenv("MIFT_ATTN_OT");
-  const bool ot = ote ? atoi(ote) != 0 : seq;
+  const bool ot = mift_env_int("MIFT_ATTN_OT", seq) != 0;
   if (seq) {
     auto kern = ot ? attn_fwd_seq_kernel<T, HD, 8, true> : attn_fwd_seq_kernel<T, HD, 8, false>;
     static bool attr = false;
@@ -1363,18 +1352,10 @@ void fwd_launch(const at::Tensor& qkv, at::Tensor& o, at::Tensor& lse, const int
                        thr != 0 ? dmask : nullptr, split);
     return;
   }
-  if (qg == 2) {
-    const int nqt = (S + 2 * BQ - 1) / (2 * BQ);
-    hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 2>), dim3(B * H * nqt), dim3(256), smem, st, (const T*)qkv.data_ptr(),
-                       (T*)o.data_ptr(), lse.data_ptr<float>(), kvl, B, S, H, scale, seed, mift_seed_step(), thr,
-                       inv_keep, attn_xcd_env());
-  } else {
-    const int nqt = (S + BQ - 1) / BQ;
-    auto k1 = ot ? attn_fwd_kernel<T, HD, 1, true> : attn_fwd_kernel<T, HD, 1, false>;
-    hipLaunchKernelGGL(k1, dim3(B * H * nqt), dim3(256), smem, st, (const T*)qkv.data_ptr(),
-                       (T*)o.data_ptr(), lse.data_ptr<float>(), kvl, B, S, H, scale, seed, mift_seed_step(), thr,
-                       inv_keep, attn_xcd_env());
-  }
+  const int nqt = (S + BQ - 1) / BQ;
+  auto k1 = ot ? attn_fwd_kernel<T, HD, 1, true> : attn_fwd_kernel<T, HD, 1, false>;
+  hipLaunchKernelGGL(k1, dim3(B * H * nqt), dim3(256), smem, st, (const T*)qkv.data_ptr(), (T*)o.data_ptr(),
+                     lse.data_ptr<float>(), kvl, B, S, H, scale, seed, mift_seed_step(), thr, inv_keep);
 }
 
 template <typename T, int HD>
@@ -1410,23 +1391,15 @@ void bwd_launch(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor&
   const int smem_dq = 2 * G::ROW_BYTES + G::TR_BYTES;
   hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD>), dim3(B * H * nqt), dim3(256), smem_dq, st, (const T*)qkv.data_ptr(),
                      (const T*)o.data_ptr(), (const T*)dout.data_ptr(), lse.data_ptr<float>(),
-                     Dv.data_ptr<float>(), (T*)dqkv.data_ptr(), kvl, B, S, H, scale, seed, mift_seed_step(), thr, inv_keep,
-                     attn_xcd_env());
+                     Dv.data_ptr<float>(), (T*)dqkv.data_ptr(), kvl, B, S, H, scale, seed, mift_seed_step(), thr, inv_keep);
   const int smem_kv = 2 * G::ROW_BYTES + 2 * G::TR_BYTES + 2 * 64 * 4;
-  // minimum waves per SIMD of the tiled dK/dV kernel (MIFT_ATTN_DKDV_OCC, read per call: A/B).  With the
+  // minimum waves per SIMD of the tiled dK/dV kernel (its OCC template default).  With the
   // round-3 bound (HD <= 64 ? 3 : 1) hd 128 took 268 registers — one wave per SIMD, below the two its LDS
   // allows; two: OPT-6.7B attention backward 629 -> 428 us (137 -> 201 TF/s), OPT-2.7B 184 -> 171 us;
   // three spills (1084 / 230 us) (profiles/r4/bench_attn_dkdv_occupancy.txt)
-  const char* oe = getenv("MIFT_ATTN_DKDV_OCC");
-  const int occ = oe ? atoi(oe) : 0;
-  auto kv = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(B * H * nkt), dim3(256), smem_kv, st, (const T*)qkv.data_ptr(),
-                       (const T*)dout.data_ptr(), lse.data_ptr<float>(), Dv.data_ptr<float>(), (T*)dqkv.data_ptr(),
-                       kvl, B, S, H, scale, seed, mift_seed_step(), thr, inv_keep, attn_xcd_env());
-  };
-  if (occ == 2) kv(attn_bwd_dkdv_kernel<T, HD, 2>);
-  else if (occ == 3) kv(attn_bwd_dkdv_kernel<T, HD, 3>);
-  else kv(attn_bwd_dkdv_kernel<T, HD>);
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, HD>), dim3(B * H * nkt), dim3(256), smem_kv, st, (const T*)qkv.data_ptr(),
+                     (const T*)dout.data_ptr(), lse.data_ptr<float>(), Dv.data_ptr<float>(), (T*)dqkv.data_ptr(),
+                     kvl, B, S, H, scale, seed, mift_seed_step(), thr, inv_keep);
 }
 
 }  // namespace

@@ -319,18 +319,10 @@ void mift_decode_tail(const at::Tensor& logits, int64_t V, at::Tensor& done, at:
   hipStream_t st = c10::hip::getCurrentHIPStream().stream();
   auto launch = [&](auto tag) {
     using T = decltype(tag);
-    // block size: MIFT_TAIL_NTH (A/B, read per call) — 256 / 512 / 1024 threads per row
-    const char* e = getenv("MIFT_TAIL_NTH");
-    const int nth = e ? atoi(e) : 1024;
-    auto go = [&](auto kern, int threads) {
-      kern<<<(unsigned)B, threads, 0, st>>>(
-          reinterpret_cast<const T*>(logits.data_ptr()), logits.stride(0), (int)V, done.data_ptr<bool>(),
-          ids.data_ptr<int64_t>(), out.data_ptr<int64_t>(), (int)out.size(1), col.data_ptr<int64_t>(),
-          pos.data_ptr<int64_t>(), t.data_ptr<int>(), fill, pad, eos);
-    };
-    if (nth == 256) go(decode_tail_kernel<T, 256>, 256);
-    else if (nth == 512) go(decode_tail_kernel<T, 512>, 512);
-    else go(decode_tail_kernel<T, 1024>, 1024);
+    decode_tail_kernel<T, 1024><<<(unsigned)B, 1024, 0, st>>>(  // 1024 threads per row
+        reinterpret_cast<const T*>(logits.data_ptr()), logits.stride(0), (int)V, done.data_ptr<bool>(),
+        ids.data_ptr<int64_t>(), out.data_ptr<int64_t>(), (int)out.size(1), col.data_ptr<int64_t>(),
+        pos.data_ptr<int64_t>(), t.data_ptr<int>(), fill, pad, eos);
   };
   if (logits.scalar_type() == at::kBFloat16) launch(bf16{});
   else {

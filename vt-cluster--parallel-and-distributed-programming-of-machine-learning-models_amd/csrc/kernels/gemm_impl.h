@@ -91,7 +91,6 @@ struct LmArgs {
   int ntn;                // column tiles of the forward (= groups of the backward)
   int gpc;                // groups per split-K chunk
   float* partial;         // [S][M][N] fp32 split-K slabs
-  int dbg;                // MIFT_LM_DBG (diagnostics only): bit 0 = skip the E store, bit 2 = no FULL-tile epilogue
   int shift;              // > 0: labels are the UNSHIFTED [B*S] ids, S = shift (see lm_label)
   int64_t ignore;         // >= 0: this id is no target (OPT ignores its pad id, a real vocabulary entry)
 };
@@ -137,14 +136,12 @@ struct EpiArgs {
   // ReLU sign bits [M][N/8] (bit e of byte (row, col/8) = stored output (row, col + e) > 0): written by an
   // ACT_RELU epilogue, read by ACT_RELU_BWD in place of the 16-bit aux (1/16 of its bytes)
   uint8_t* sbits;
-  int pfg;        // 256x256 epilogue: operands requested per group of 4 chunks (MIFT_EPI_PFG, default 1)
   int ntc;        // non-temporal C stores (outputs >= 96 MiB; MIFT_EPI_NT forces)
   // diagnostics (tools/gemm_stamps.py): per block, wave 0's s_memtime at [0] entry, [1] main loop
   // started (prologue done), [2] main loop done, [3] C tile in LDS, [4] exit; s_memrealtime at [6] / [7]
   long long* stamps;
   int staged;     // interior tiles: feature-staged epilogue phase 2 (MIFT_EPI_STAGED, default 1)
   int hoist;      // dropout-mask hashes with the hoisted high-word mix (output < 2^33 elements; MIFT_EPI_HOIST)
-  int ext_lds;    // NSTAGE >= 2 tiles: K-extension operands staged into LDS during the last k-tile (MIFT_EXT_LDS)
 };
 
 // Tile t (after the XCD remap, consecutive t share an XCD) -> (row tile, column tile).  With g > 0
@@ -938,9 +935,8 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
     constexpr int VPR = BN / 8;
     constexpr int ITER = BM * VPR / NT;
     static_assert((BM * VPR) % NT == 0, "epilogue chunks must split evenly over the threads");
-    // (an up-front operand prefetch for all chunks, MIFT_EPI_PREFETCH, measured +1.5 % on the distilgpt2
-    // step and +2..5 % on the 256x256 tile, rounds 2 / 5, and was removed in round 6; interior tiles
-    // take the staged form below)
+    // (an up-front operand prefetch for all chunks measured +1.5 % on the distilgpt2 step and +2..5 % on
+    // the 256x256 tile, rounds 2 / 5, and was removed in round 6; interior tiles take the staged form below)
     constexpr bool PF_OK = ITER <= 8;
     // one 8-column chunk: (aux, res) come prefetched when have_aux / have_res
     auto chunk = [&](int it, bool have_aux, short8 auxv, bool have_res, short8 resv, int sbp) {
@@ -1023,7 +1019,6 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
         for (int e = 0; e < 8; ++e) sb |= ((float)(T)z[e] > 0.f ? 1u : 0u) << e;
         ep.sbits[(size_t)gr * (N >> 3) + (gc >> 3)] = (uint8_t)sb;
       }
-      if (ep.lm.dbg & 1) return;  // diagnostics: MIFT_LM_DBG bit 0 skips the C store
       if (full && ep.ntc) {  // MIFT_EPI_NT=1 (A/B): non-temporal C stores
         short8 o;
   #pragma unroll
@@ -1241,7 +1236,6 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
             ep.sbits[(size_t)(m0 + row[k]) * (N >> 3) + ((n0 + c8[k]) >> 3)] = (uint8_t)sb;
           }
         }
-        if (ep.lm.dbg & 1) continue;
         if (ep.ntc) {
   #pragma unroll
           for (int k = 0; k < G; ++k) __builtin_nontemporal_store(o[k], reinterpret_cast<short8*>(C + off[k]));
@@ -1264,12 +1258,12 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
       // 256x256 (16 chunks per thread, one block per CU: no second block hides a chunk's operand round
       // trip, ~1 us from HBM, paid 16 times per tile in the rolled loop — OPT's residual-dropout
       // epilogues cost +51..62 us per GEMM at micro-batch 48): groups of 4 chunks request their aux /
-      // residual / sign-bit operands together, one round trip per group.  MIFT_EPI_PFG=0: per chunk (A/B)
+      // residual / sign-bit operands together, one round trip per group
       constexpr int G = 4;
       static_assert(ITER % G == 0, "chunk groups");
-      const bool g_aux = ep.pfg && ep.aux != nullptr && ep.act != ACT_NONE && N >= 8;
-      const bool g_res = ep.pfg && ep.residual != nullptr && N >= 8;
-      const bool g_sb = ep.pfg && ep.sbits != nullptr && ep.act == ACT_RELU_BWD && ep.aux == nullptr;
+      const bool g_aux = ep.aux != nullptr && ep.act != ACT_NONE && N >= 8;
+      const bool g_res = ep.residual != nullptr && N >= 8;
+      const bool g_sb = ep.sbits != nullptr && ep.act == ACT_RELU_BWD && ep.aux == nullptr;
       for (int g0 = 0; g0 < ITER; g0 += G) {
         short8 av[G], rv[G];
         int bv[G];
@@ -1317,7 +1311,6 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
     // columns), and there it needs no per-element bounds selects; the label's logit is picked by
     // selects across the row's column tiles and stored once per row fragment (one divergent store
     // per i instead of one exec-mask branch per (i, j)).
-    const bool dbg_raw = (lm.dbg & 2) != 0;
     auto exp_pass = [&](auto fullc) {
       constexpr bool FULL = decltype(fullc)::value;
 #pragma unroll
@@ -1353,8 +1346,7 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
           float ev[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            ev[e] = dbg_raw ? acc[i][j][e]
-                    : (FULL || col + e < V) ? __builtin_amdgcn_exp2f(__builtin_fmaf(acc[i][j][e], L2E, -mb)) : 0.f;
+            ev[e] = (FULL || col + e < V) ? __builtin_amdgcn_exp2f(__builtin_fmaf(acc[i][j][e], L2E, -mb)) : 0.f;
             s += ev[e];
           }
           const int d = lab - col;  // static selects: a runtime vector index would go to scratch
@@ -1371,7 +1363,7 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
         if (fq == 0) reds[wave * WM + i * 16 + fr] = s;
       }
     };
-    if (n0 + BN <= V && !(lm.dbg & 4)) exp_pass(std::true_type{});  // block-uniform; dbg bit 2: A/B
+    if (n0 + BN <= V) exp_pass(std::true_type{});  // block-uniform
     else exp_pass(std::false_type{});
     __syncthreads();
     if (tid < BM) {  // one thread per block row: combine the NWN wave partials
@@ -1386,7 +1378,6 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
       if (m == -INFINITY) m = 0.f;
       if (row < M) lm.stats[(size_t)row * lm.ntn + n0 / BN] = make_float2(m, s);
     }
-    if (lm.dbg & 1) return;
     constexpr int VPR = BN / 8;
     static_assert((BM * VPR) % NT == 0, "E copy-out chunks must split evenly over the threads");
 #pragma unroll 4
@@ -1482,7 +1473,6 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
       mainloop8(w0 * GK, min(nk_all, w1 * GK), [&](int kt) {
         const int gk = w0 * GK + kt;
         if (gk % GK != 0) return;
-        if (lm.dbg & 8) return;  // diagnostics (MIFT_LM_DBG bit 3): no rescale — wrong numbers, timing only
         const int g = gk / GK - w0;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -1532,7 +1522,7 @@ __global__ __launch_bounds__(NWM* NWN * 64, (gemm_waves_per_eu<BM, BN, NWM, NWN,
     } else if constexpr (NSTAGE == 1) {
       mainloop4(0, nk_all);
     } else {
-      mainloop(0, nk_all, (A2 != nullptr || bias_lds) && ep.ext_lds);
+      mainloop(0, nk_all, A2 != nullptr || bias_lds);
     }
     stamp(2);
     epilogue();
@@ -1751,7 +1741,7 @@ __global__ __launch_bounds__(512) void lmhead_fwd_persist_kernel(const T* __rest
         const auto r0 = __builtin_amdgcn_permlane16_swap(pk[2 * p][0], pk[2 * p + 1][0], false, false);
         const auto r1 = __builtin_amdgcn_permlane16_swap(pk[2 * p][1], pk[2 * p + 1][1], false, false);
         const int c0 = n0 + wn * WN + (2 * p + (fq & 1)) * 16 + (fq >> 1) * 8;
-        if (!(lm.dbg & 1) && row < M && (FULL || c0 < N)) {
+        if (row < M && (FULL || c0 < N)) {
           const v4u32 val = {(unsigned)r0[0], (unsigned)r1[0], (unsigned)r0[1], (unsigned)r1[1]};
           *reinterpret_cast<v4u32*>(E + (size_t)row * lde + c0) = val;
         }
@@ -1868,10 +1858,10 @@ __global__ __launch_bounds__(512) void lmhead_fwd_persist_kernel(const T* __rest
         early = 1;
       }
     }
-    const bool full = n0 + BN <= lm.V && !(lm.dbg & 4);  // block-uniform
+    const bool full = n0 + BN <= lm.V;  // block-uniform
     if (full) epilogue(m0, n0, std::true_type{});
     else epilogue(m0, n0, std::false_type{});
-    if (early && full && !(lm.dbg & 1)) early = 2;
+    if (early && full) early = 2;
     if (wm == 1 && j + 1 < ntl) __builtin_amdgcn_s_barrier();  // re-stagger for the next tile
     asm volatile("" ::: "memory");
     m0 = nm0;
@@ -1898,16 +1888,8 @@ int* sk_flags(int n) {
   return flags.data_ptr<int>();
 }
 
-int sk_mode_env() {
-  static int v = [] { const char* e = getenv("MIFT_GEMM_SK"); return e ? atoi(e) : -1; }();
-  return v;  // -1 auto, 0 off, 1 force
-}
-
-// tile raster group (EpiArgs::group_m): MIFT_GEMM_GROUP (read per call, A/B-able) or the default
-int gemm_group_m(int N) {
-  if (const char* e = getenv("MIFT_GEMM_GROUP")) return atoi(e);
-  return N >= 8192 ? 4 : 0;
-}
+// tile raster group (EpiArgs::group_m)
+int gemm_group_m(int N) { return N >= 8192 ? 4 : 0; }
 
 // out[m, 0:32] = alpha · Σ_t slab[t][m][0:PW] (columns >= PW zero): the per-column-tile partials of
 // the epilogue projection, summed in tile order.  4 outputs per thread (every thread of a 16-wide slab
@@ -1971,8 +1953,7 @@ void launch_gemm(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, const 
   const int G = num_cus() * (BPC > 0 ? BPC : 1);
   const int rem = nblk % G;
   int sk_tiles = 0, S = 1;
-  const int mode = sk_mode_env();
-  if (HAS_SK && mode != 0 && rem != 0 && (mode == 1 || rem * 100 < G * 85)) {
+  if (HAS_SK && rem != 0 && rem * 100 < G * 85) {
     double best = 1.0;
     // chunks of >= 16 k-tiles: below that the fp32 partial round trip costs more than the
     // balanced wave saves (measured: K=768 GEMMs lost 2-4x with 3-k-tile chunks)
@@ -2039,7 +2020,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const T* __restric
                                                               int ldb, int ldc, EpiArgs ep, const T* __restrict__ lnw,
                                                               const T* __restrict__ lnb, float eps, int ksplit,
                                                               float* __restrict__ kws, unsigned* __restrict__ kflags,
-                                                              int pfe, const float* __restrict__ lfc1,
+                                                              const float* __restrict__ lfc1,
                                                               const float* __restrict__ lfc2) {
   constexpr bool LNP = LNM != 0;
   constexpr int NT = BN / 16;  // 16-column MFMA tiles per block
@@ -2075,8 +2056,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const T* __restric
   constexpr int CPR = BN / 8;  // 8-column chunks per row
   constexpr bool PFE = 64 * CPR <= NW * 64;
   short8 pf_bias = short8{0, 0, 0, 0, 0, 0, 0, 0}, pf_res = pf_bias;
-  const bool pf_b = PFE && pfe && ep.bias != nullptr && !ep.bias_f32;
-  const bool pf_r = PFE && pfe && ep.residual != nullptr;
+  const bool pf_b = PFE && ep.bias != nullptr && !ep.bias_f32;
+  const bool pf_r = PFE && ep.residual != nullptr;
   float4 pf_f1[2] = {}, pf_f2[2] = {};  // LNM = 2: this thread's chunk of lfc1 / lfc2
   if constexpr (PFE) {
     const int row = tid / CPR, c8 = (tid % CPR) * 8;
@@ -2378,9 +2359,6 @@ void launch_skinny(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, cons
   }
   constexpr int RED = NW * 64 * (BN + 4) * 4, OT = 64 * (BN + 1) * 4;
   static_assert(RED + OT <= 160 * 1024, "LDS budget");
-  // epilogue-operand prefetch (MIFT_SKINNY_PF=0: off; read per call, A/B)
-  const char* pfs = getenv("MIFT_SKINNY_PF");
-  const int pfe = pfs ? atoi(pfs) : 1;
   const int smem = RED + (ep.pw != nullptr ? OT : 0);
   static bool attr = false;
   if (!attr) {
@@ -2400,7 +2378,7 @@ void launch_skinny(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, cons
       auto kern = lfc1 != nullptr ? gemm_skinny_kernel<T, BN, NW, 2> : gemm_skinny_kernel<T, BN, NW, 1>;
       hipLaunchKernelGGL(kern, dim3(nb), dim3(NW * 64), smem, st, (const T*)a.data_ptr(), (const T*)b.data_ptr(),
                          (T*)c.data_ptr(), a2, b2, M, N, K, (int)a.stride(0), (int)b.stride(0), (int)c.stride(0), epx,
-                         lnw, lnb, eps, 1, (float*)nullptr, (unsigned*)nullptr, pfe, lfc1, lfc2);
+                         lnw, lnb, eps, 1, (float*)nullptr, (unsigned*)nullptr, lfc1, lfc2);
     } else {
       TORCH_CHECK(false, "gemm_skinny: LN prologue needs the 16-column 8-wave form");
     }
@@ -2408,7 +2386,7 @@ void launch_skinny(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, cons
     hipLaunchKernelGGL((gemm_skinny_kernel<T, BN, NW, 0>), dim3(nb * ksplit), dim3(NW * 64), smem, st,
                        (const T*)a.data_ptr(), (const T*)b.data_ptr(), (T*)c.data_ptr(), a2, b2, M, N, K,
                        (int)a.stride(0), (int)b.stride(0), (int)c.stride(0), epx, (const T*)nullptr,
-                       (const T*)nullptr, 0.f, ksplit, kws, kflags, pfe, (const float*)nullptr, (const float*)nullptr);
+                       (const T*)nullptr, 0.f, ksplit, kws, kflags, (const float*)nullptr, (const float*)nullptr);
   }
   if (ep.pw != nullptr)
     hipLaunchKernelGGL(proj_reduce_kernel<T>, dim3((unsigned)(((int64_t)M * 8 + 255) / 256)), dim3(256), 0, st,
@@ -2417,10 +2395,10 @@ void launch_skinny(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, cons
 
 // the skinny kernel applies: a forward epilogue without dropout on <= 64 rows (MIFT_GEMM_SKINNY=0: off)
 bool skinny_ok(int M, int N, int K, const EpiArgs& ep) {
-  static const int env = [] { const char* e = getenv("MIFT_GEMM_SKINNY"); return e ? atoi(e) : 1; }();
+  const int env = mift_env_int("MIFT_GEMM_SKINNY", 1);  // read per call (A/B); 2: also N > 4096
   if (!env || M > 64 || N % 16 != 0) return false;
   if (N > 4096 ? (K > 1024 || N % 64 != 0 || env < 2) : (K > 4096 || (K > 1024 && (K / 32) % ((K + 1023) / 1024)))) return false;
-  if (ep.thr != 0 || ep.ext_thr != 0 || ep.aux != nullptr || ep.sbits != nullptr || ep.lm.dbg != 0) return false;
+  if (ep.thr != 0 || ep.ext_thr != 0 || ep.aux != nullptr || ep.sbits != nullptr) return false;
   if (ep.act != ACT_NONE && ep.act != ACT_GELU_TANH && ep.act != ACT_RELU && ep.act != ACT_GELU_ERF) return false;
   if (ep.pw != nullptr && ep.pthr != 0) return false;
   return true;
@@ -2474,9 +2452,9 @@ void dispatch_tile(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, cons
       // but one wave per SIMD cannot hide the dependent hash chains of a dropout mask: with a residual
       // dropout or a masked K-extension tile 8 stays faster (out / fc2 / dgrads, 4-19 %;
       // profiles/r6/bench_gemm4_epilogues.json).  MIFT_GEMM_T10=0 / 1 forces either (read per call, A/B)
-      const char* e = getenv("MIFT_GEMM_T10");
+      const int t10 = mift_env_int("MIFT_GEMM_T10", -1);
       const bool hashes = ep.thr != 0 || ep.ext_thr != 0;
-      tile = (e ? atoi(e) != 0 : !hashes) ? 10 : 8;
+      tile = (t10 >= 0 ? t10 != 0 : !hashes) ? 10 : 8;
     }
     // one chip-wave of 128x96 tiles (1-2 per CU): the OPT micro-batch-4 shapes (M = 2048, N = 2560)
     // ran 20-30 % faster than on the 128x256 split-K / 128x128 tiles (fc2 fwd 167 -> 122 us, qkv dgrad
@@ -2651,7 +2629,6 @@ std::vector<at::Tensor> lmhead_fwd_impl(const at::Tensor& a, const at::Tensor& w
   ep.lm.ntn = ntn;
   ep.lm.shift = shift;
   ep.lm.ignore = ignore;
-  if (const char* d = getenv("MIFT_LM_DBG")) ep.lm.dbg = atoi(d);
   {
     // tile raster of the head: the 32 blocks an XCD runs at once cover g row panels x 32/g vocab tiles,
     // so each W tile is fetched from the Infinity Cache once per g row panels (row-panel order, g = 1,
@@ -2659,9 +2636,7 @@ std::vector<at::Tensor> lmhead_fwd_impl(const at::Tensor& a, const at::Tensor& w
     // persistent kernel measured g = 4 best at K = 768 in isolation (648 vs 714 us), g = 8 at K = 2560
     // (1381 vs 1491) (profiles/r5/bench_lm_persist.jsonl); inside the distilgpt2 step g = 3 is best
     // (4.630 vs 4.649 / 4.660 / 4.731 ms for g = 2 / 4 / 1, profiles/r6/step_ab_dgpt_lm_group*.json).
-    // MIFT_LM_GROUP (per call) overrides.
-    const char* g = getenv("MIFT_LM_GROUP");
-    ep.group_m = g ? atoi(g) : (K <= 1024 ? 3 : 8);
+    ep.group_m = K <= 1024 ? 3 : 8;
   }
   SkArgs sk{};
   // staging ring (128 KiB) reused for the E tile + the two row-partial arrays
@@ -2684,8 +2659,8 @@ std::vector<at::Tensor> lmhead_fwd_impl(const at::Tensor& a, const at::Tensor& w
   // and epilogue are a large share; 664 vs 723 us), the one-tile kernel above (OPT K = 2560: 40 k-tiles
   // per tile, 1350 vs 1394 us with the raster group of both) — profiles/r5/bench_lm_persist_v2.jsonl.
   // MIFT_LM_PERSIST=0/1 forces either (read per call: A/B-able).  Even M: the ids copy moves 16-B pairs.
-  const char* pe = getenv("MIFT_LM_PERSIST");
-  const bool persist = (pe ? atoi(pe) != 0 : K <= 1024) && K / BK >= 2 && M >= 2 && M % 2 == 0;
+  const int pe = mift_env_int("MIFT_LM_PERSIST", -1);
+  const bool persist = (pe >= 0 ? pe != 0 : K <= 1024) && K / BK >= 2 && M >= 2 && M % 2 == 0;
   if (persist) {
     const int G = std::min(grid, num_cus());  // one 512-thread, 137 KiB block per CU
     hipLaunchKernelGGL(kernp, dim3(G), dim3(512), SMEM_P, st, (const T*)a.data_ptr(), (const T*)w.data_ptr(),
@@ -2729,7 +2704,6 @@ at::Tensor lmhead_dgrad_impl(const at::Tensor& E, const at::Tensor& wt, const at
   // split the vocabulary so the grid is a whole number of chip waves (one block per CU), >= 3 waves
   const int cus = num_cus();
   int S = std::max(1, std::min(ntn_f, (3 * cus + tiles - 1) / tiles));
-  if (const char* e = getenv("MIFT_LM_SPLIT")) S = std::max(1, std::min(ntn_f, atoi(e)));  // A/B knob, per call
   const int gpc = (ntn_f + S - 1) / S;
   S = (ntn_f + gpc - 1) / gpc;
   auto partial = at::empty({S, M, N}, E.options().dtype(at::kFloat));
@@ -2918,8 +2892,6 @@ std::vector<at::Tensor> mift_gemm_nt(const at::Tensor& a, const at::Tensor& b, c
   ep.sstep = mift_seed_step();
   ep.group_m = gemm_group_m(N);
   {
-    const char* e = getenv("MIFT_EPI_PFG");  // read per call (A/B)
-    ep.pfg = e ? atoi(e) : 1;
     // non-temporal C stores for large outputs (OPT-2.7B mb 48, every output 126-503 MB: 4-block step
     // 302.9 -> 300.7 ms); the distilgpt2 outputs (<= 50 MB) are re-read from the Infinity Cache by the
     // next kernel (4.872 -> 4.904 ms with NT stores), so the default is by size (profiles/r5/
@@ -2927,10 +2899,8 @@ std::vector<at::Tensor> mift_gemm_nt(const at::Tensor& a, const at::Tensor& b, c
     // threshold at the Infinity Cache size (256 MiB): a smaller output can still be re-read from it by
     // the next kernel, which NT stores would give up (the 96 MiB form measured +0.7 % on the
     // mb-48 step, inside the box spread: its gain came from the 503 MB fc1 / fc2-dgrad outputs)
-    const char* n = getenv("MIFT_EPI_NT");
-    ep.ntc = n ? atoi(n) : ((int64_t)M * N * (int64_t)a.element_size() >= (256ll << 20) ? 1 : 0);
+    ep.ntc = mift_env_int("MIFT_EPI_NT", (int64_t)M * N * (int64_t)a.element_size() >= (256ll << 20) ? 1 : 0);
   }
-  if (const char* d = getenv("MIFT_LM_DBG")) ep.lm.dbg = atoi(d);  // diagnostics (bit 0: no C store)
   ep.pre_add = nullptr;
   if (pre_add) {
     TORCH_CHECK(pre_add->size(0) == M && pre_add->size(1) == N && pre_add->stride(0) == c.stride(0) &&
@@ -2953,14 +2923,8 @@ std::vector<at::Tensor> mift_gemm_nt(const at::Tensor& a, const at::Tensor& b, c
     ep.palpha = (float)proj_alpha * (proj_p > 0 ? mift_inv_keep(proj_p) : 1.f);
   }
   ep.stamps = g_gemm_stamps;
-  {
-    const char* e = getenv("MIFT_EPI_STAGED");  // read per call (A/B)
-    ep.staged = e ? atoi(e) : 1;
-    const char* h = getenv("MIFT_EPI_HOIST");   // read per call (A/B); needs M·N < 2^33
-    ep.hoist = (h ? atoi(h) : 1) && (uint64_t)M * N < (1ull << 33);
-    const char* x = getenv("MIFT_EXT_LDS");     // read per call (A/B)
-    ep.ext_lds = x ? atoi(x) : 1;
-  }
+  ep.staged = mift_env_int("MIFT_EPI_STAGED", 1);  // read per call (A/B)
+  ep.hoist = mift_env_int("MIFT_EPI_HOIST", 1) && (uint64_t)M * N < (1ull << 33);  // needs M·N < 2^33
   ep.sbits = nullptr;
   if (sbits) {  // ReLU sign bits: written (act = relu) or read in place of aux (act = relu backward)
     TORCH_CHECK((act == ACT_RELU || (act == ACT_RELU_BWD && !aux)) && N % 8 == 0 && sbits->is_cuda() &&

@@ -317,8 +317,6 @@ __global__ __launch_bounds__(256) void ln_bwd8_kernel(const T* __restrict__ dy, 
 
 // (RPW, NIT) of the 16-B form for this D, or false (4-element form)
 inline bool ln8_shape(int D, int& rpw, int& nit) {
-  const char* e = getenv("MIFT_LN_V");  // 1 = the 4-element kernels (A/B knob, read per call)
-  if (e && atoi(e) == 1) return false;
   rpw = D <= 1024 ? 2 : 1;
   const int per = 8 * (64 / rpw);
   if (D % per != 0) return false;

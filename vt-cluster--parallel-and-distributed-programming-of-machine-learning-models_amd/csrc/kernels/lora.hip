@@ -201,7 +201,7 @@ MIFT_HD v4s tr_read(const char* lds_base, int off) {
 // a problem is split into P/64 column tiles x ceil(M / rows) row chunks.  One launch per layer
 // instead of two per adapter: the per-adapter launches were ~10 us each for 12-50 MB of reads
 // (ramp + tail dominate), 0.43 ms of the 5.8 ms distilgpt2 step on the critical path even on the
-// side stream (tools/step_ab.py, MIFT_DIAG_SKIP=wgrad).
+// side stream that round 3 ran them on.
 constexpr int WG_MAXP = 16, WG_MAXS = 4;
 struct WgSlot {
   int qoff, rank;   // columns [qoff, qoff + rank) of the 32-wide product ...
@@ -488,17 +488,14 @@ at::Tensor mift_lora_proj(const at::Tensor& x, const at::Tensor& w, double alpha
     (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
     return v > 0 ? v : 256;
   }();
-  // 16-row blocks while 32-row blocks would leave fewer than two per CU (MIFT_LORA_MT=1|2 forces)
-  const char* mte = getenv("MIFT_LORA_MT");
-  const int MT = mte ? (atoi(mte) == 1 ? 1 : 2) : ((M + 31) / 32 >= 2 * cus ? 2 : 1);
+  // 16-row blocks while 32-row blocks would leave fewer than two per CU
+  const int MT = (M + 31) / 32 >= 2 * cus ? 2 : 1;
   const int mblocks = (M + 16 * MT - 1) / (16 * MT), nks = K / 32;
-  static const int ks_env = [] { const char* e = getenv("MIFT_LORA_KS"); return e ? atoi(e) : 0; }();
   // K-splits only when the row blocks alone leave CUs idle (>= ~1024 blocks, >= 4 k-steps each).  With
   // at least one row block per CU the split's hand-off costs more than the extra blocks give: OPT-2.7B
   // at micro-batch 12 (M = 6144, 384 row blocks, K = 2560) ran its projections at 22.3 / 39.1 us with
   // KS = 3 and 19.4 / 35.2 us unsplit, step 675 -> 669 ms (profiles/r4/lora_proj_ks_opt27b_mb12.txt)
-  int KS = mblocks >= cus ? 1 : std::max(1, std::min(std::max(1, nks / 4), (1024 + mblocks - 1) / mblocks));
-  if (ks_env > 0) KS = std::max(1, std::min(ks_env, std::max(1, nks / 4)));  // A/B override
+  const int KS = mblocks >= cus ? 1 : std::max(1, std::min(std::max(1, nks / 4), (1024 + mblocks - 1) / mblocks));
   float* ws = nullptr;
   unsigned* flags = nullptr;
   at::Tensor wsb;
@@ -517,16 +514,9 @@ at::Tensor mift_lora_proj(const at::Tensor& x, const at::Tensor& w, double alpha
     auto launch = [&](auto kern, int threads) {
       std::apply([&](auto... a) { hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, st, a...); }, args);
     };
-    // MIFT_LORA_NW=8 (A/B only): 8-wave blocks, each wave half the k-steps — measured slower at OPT-2.7B
-    // mb 12 (20.7 / 37.8 vs 19.4 / 35.2 us, step 647 vs 644 ms: profiles/r4/lora_proj_nw8_rejected.txt)
-    static const int nw_env = [] { const char* e = getenv("MIFT_LORA_NW"); return e ? atoi(e) : 0; }();
-    const bool nw8 = nw_env == 8;
-    if (nw8) {
-      if (MT == 1 && one_tile) launch(lora_proj_kernel<T, 8, 1, 1>, 512);
-      else if (MT == 1) launch(lora_proj_kernel<T, 8, 1, 2>, 512);
-      else if (one_tile) launch(lora_proj_kernel<T, 8, 2, 1>, 512);
-      else launch(lora_proj_kernel<T, 8, 2, 2>, 512);
-    } else if (MT == 1 && one_tile) launch(lora_proj_kernel<T, 4, 1, 1>, 256);
+    // (8-wave blocks, each wave half the k-steps, measured slower at OPT-2.7B mb 12: 20.7 / 37.8 vs
+    // 19.4 / 35.2 us, step 647 vs 644 ms, profiles/r4/lora_proj_nw8_rejected.txt)
+    if (MT == 1 && one_tile) launch(lora_proj_kernel<T, 4, 1, 1>, 256);
     else if (MT == 1) launch(lora_proj_kernel<T, 4, 1, 2>, 256);
     else if (one_tile) launch(lora_proj_kernel<T, 4, 2, 1>, 256);
     else launch(lora_proj_kernel<T, 4, 2, 2>, 256);
@@ -543,9 +533,8 @@ namespace {
 template <typename T>
 void launch_wgrad(WgArgs& args, hipStream_t st) {
   // rows per block: ~2048 blocks over the group (eight per CU: loads of several blocks in flight
-  // per CU), a multiple of the 128-row load group, >= 128 (MIFT_WGRAD_BLOCKS: A/B knob)
-  const char* te = getenv("MIFT_WGRAD_BLOCKS");
-  const int64_t target = te ? std::max(1, atoi(te)) : 2048;
+  // per CU), a multiple of the 128-row load group, >= 128
+  const int64_t target = 2048;
   int64_t work = 0;
   for (int i = 0; i < args.np; ++i) work += (int64_t)(args.p[i].P / 64) * args.p[i].M;
   const int64_t rows = std::max<int64_t>(128, (work / target + 127) / 128 * 128);

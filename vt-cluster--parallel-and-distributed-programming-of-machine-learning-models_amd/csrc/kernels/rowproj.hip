@@ -498,42 +498,23 @@ __global__ __launch_bounds__(NW * 64) void rowproj_mfma_kernel(const T* __restri
 
 // MFMA-form widths: D = 32·NK, split over NW waves (NK / NW k-steps of 32 columns per wave, so a wave
 // holds <= 10 16-B pieces of each row operand): 768 / 1024 on 4 waves (distilgpt2, OPT-125m / 350m),
-// 2048 / 2560 on 8 (OPT-1.3b / 2.7b), 4096 on 16 (OPT-6.7b).  MIFT_ROWPROJ_V=1 (A/B knob, read per
-// call): the row kernels.  Other widths take the row kernels (the LN / mask producers) or lora_proj.
+// 2048 / 2560 on 8 (OPT-1.3b / 2.7b), 4096 on 16 (OPT-6.7b).  Other widths take the row kernels (the
+// LN / mask producers) or lora_proj.
 inline bool rowproj_width(int D) { return D == 768 || D == 1024 || D == 2048 || D == 2560 || D == 4096; }
-inline bool rowproj_mfma_ok(int D) {
-  const char* e = getenv("MIFT_ROWPROJ_V");
-  return !(e && atoi(e) == 1) && rowproj_width(D);
-}
 
 // waves per block at the distilgpt2 / OPT-125m widths: 12 (16 at 1024; 2 k-steps per wave).  More waves
 // per row block shorten each wave's load chain and register footprint (the LN-backward pass: ~100 VGPRs
 // on 8 waves against 174 on 4) so more waves per SIMD hide the row loads — distilgpt2 step 4.727 ->
 // 4.664 ms on 8 waves (LN-bwd + dropout-bwd + dT 17.5 -> 15 us, LN + T 11.1 -> 9.5, c_attn dT 14.3 ->
-// 10.7), 4.659 on 12 (profiles/r5/step_ab_rowproj_nw*.json).  MIFT_ROWPROJ_NW = 4 / 8 / 12 (read per
-// call): A/B.
-inline int rowproj_nw() {
-  const char* e = getenv("MIFT_ROWPROJ_NW");
-  const int v = e ? atoi(e) : 12;
-  return v == 4 || v == 8 ? v : 12;
-}
+// 10.7), 4.659 on 12 (profiles/r5/step_ab_rowproj_nw*.json).
 
 // f(integral_constant NK, integral_constant NW) for a rowproj_width D
 template <typename F>
 void by_nk(int D, F&& f) {
   using std::integral_constant;
-  const int nw = rowproj_nw();
   switch (D) {
-    case 768:
-      if (nw == 4) f(integral_constant<int, 24>{}, integral_constant<int, 4>{});
-      else if (nw == 12) f(integral_constant<int, 24>{}, integral_constant<int, 12>{});
-      else f(integral_constant<int, 24>{}, integral_constant<int, 8>{});
-      break;
-    case 1024:
-      if (nw == 4) f(integral_constant<int, 32>{}, integral_constant<int, 4>{});
-      else if (nw == 12) f(integral_constant<int, 32>{}, integral_constant<int, 16>{});
-      else f(integral_constant<int, 32>{}, integral_constant<int, 8>{});
-      break;
+    case 768: f(integral_constant<int, 24>{}, integral_constant<int, 12>{}); break;
+    case 1024: f(integral_constant<int, 32>{}, integral_constant<int, 16>{}); break;
     case 2048: f(integral_constant<int, 64>{}, integral_constant<int, 8>{}); break;
     case 2560: f(integral_constant<int, 80>{}, integral_constant<int, 8>{}); break;
     default: f(integral_constant<int, 128>{}, integral_constant<int, 16>{}); break;  // 4096
@@ -546,14 +527,8 @@ void by_nk(int D, F&& f) {
 inline bool rowproj_proj_width(int K) { return rowproj_width(K) || K == 2304; }
 template <typename F>
 void by_nk_proj(int K, F&& f) {
-  if (K == 2304) {
-    const int nw = rowproj_nw();
-    if (nw == 4) f(std::integral_constant<int, 72>{}, std::integral_constant<int, 4>{});
-    else if (nw == 12) f(std::integral_constant<int, 72>{}, std::integral_constant<int, 12>{});
-    else f(std::integral_constant<int, 72>{}, std::integral_constant<int, 8>{});
-  } else {
-    by_nk(K, f);
-  }
+  if (K == 2304) f(std::integral_constant<int, 72>{}, std::integral_constant<int, 12>{});
+  else by_nk(K, f);
 }
 
 template <int LR, typename F>
@@ -606,7 +581,7 @@ std::vector<at::Tensor> mift_layer_norm_fwd_proj(const at::Tensor& x, const at::
   const float inv = p > 0 ? mift_inv_keep(p) : 1.f;
   const bool wf32 = w.scalar_type() == at::kFloat;
   TORCH_CHECK(wf32 || w.scalar_type() == x.scalar_type(), "layer_norm_fwd_proj: LN weight dtype");
-  if (rowproj_mfma_ok(D)) {
+  if (rowproj_width(D)) {
     auto go2 = [&](auto tt, auto wt) {
       using T = decltype(tt);
       using Wt = decltype(wt);
@@ -666,7 +641,7 @@ std::vector<at::Tensor> mift_mask_proj(const at::Tensor& x, double p, int64_t se
   if (M == 0) return {y, pout};
   hipStream_t st = c10::hip::getCurrentHIPStream().stream();
   const float inv = p > 0 ? mift_inv_keep(p) : 1.f;
-  if (rowproj_mfma_ok(D)) {
+  if (rowproj_width(D)) {
     auto go2 = [&](auto tt) {
       using T = decltype(tt);
       by_nk(D, [&](auto nk, auto nw) {
@@ -705,7 +680,7 @@ std::vector<at::Tensor> mift_mask_proj(const at::Tensor& x, double p, int64_t se
 // the rowproj widths; the caller checks mift_ln_bwd_mask_proj_ok)
 // (not at 4096: the 16-wave MODE 3 form spills ~110 VGPRs at its 128-register budget and ran 155 us
 // against 81 for layer_norm_bwd + mask_scale + lora_proj at M = 6144, tools/bench_rowproj_opt.py)
-bool mift_ln_bwd_mask_proj_ok(int64_t D) { return rowproj_mfma_ok((int)D) && D != 4096; }
+bool mift_ln_bwd_mask_proj_ok(int64_t D) { return rowproj_width((int)D) && D != 4096; }
 
 std::vector<at::Tensor> mift_ln_bwd_mask_proj(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& w,
                                               const at::Tensor& mean, const at::Tensor& rstd,
@@ -760,9 +735,8 @@ std::vector<at::Tensor> mift_ln_bwd_mask_proj(const at::Tensor& dy, const at::Te
 bool mift_rowproj_lora_proj(const at::Tensor& x, const at::Tensor& w, at::Tensor& out, double alpha, double p,
                             int64_t seed, int64_t rows) {
   const int M = x.size(0), K = x.size(1);
-  const char* e = getenv("MIFT_ROWPROJ_V");  // 1 = off (A/B knob, read per call)
   // (K = 3072 measured slower here than lora_proj's kernel: 24.2 vs 21.9 us at M = 8192)
-  if ((e && atoi(e) == 1) || !rowproj_proj_width(K) || x.stride(0) != K ||
+  if (!rowproj_proj_width(K) || x.stride(0) != K ||
       reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0)
     return false;
   if (M == 0) return true;

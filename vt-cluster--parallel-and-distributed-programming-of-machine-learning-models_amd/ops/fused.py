@@ -28,7 +28,6 @@ import os
 import torch
 
 from . import kernels as K
-from .streams import join as join_side, run_side
 
 # The fused row passes (LN / dropout-bwd / LN-bwd + the LoRA projection, csrc/kernels/rowproj.hip) run
 # their MFMA 16-row form at the widths below (4 waves per block at 768 / 1024, 8 at 2048 / 2560, 16 at
@@ -43,13 +42,8 @@ _ROWPROJ_D = {"ln": (768, 1024, 2048, 2560), "mask": (768, 1024, 2048, 2560, 409
               "ln_bwd": (768, 1024, 2048, 2560)}
 
 
-def _diag_skip(what):
-    """MIFT_DIAG_SKIP=wgrad (diagnostics only, wrong gradients): drop the LoRA weight-grad launches
-    to measure their critical-path cost in a whole step (tools/step_ab.py).  Read per call."""
-    return what in os.environ.get("MIFT_DIAG_SKIP", "").split(",")
-
-_LNPROJ_MAX_ROWS = int(os.environ.get("MIFT_LNPROJ_MAX_ROWS", "8"))
-_LNPROJ_MAX_D = int(os.environ.get("MIFT_LNPROJ_MAX_D", "1024"))
+_LNPROJ_MAX_ROWS = 8
+_LNPROJ_MAX_D = 1024
 
 
 def _mfma_width(D, kind):
@@ -84,9 +78,8 @@ _BWD = {0: 0, 1: 4, 2: 5, 3: 6}
 
 
 def _epi_proj_kw(lo, seed, training):
-    """gemm kwargs that make the producing GEMM's epilogue emit ``lo.forward(out)`` (MIFT_EPI_PROJ=0:
-    the separate lora_proj pass, A/B knob read per call)."""
-    if lo is None or os.environ.get("MIFT_EPI_PROJ", "1") == "0":
+    """gemm kwargs that make the producing GEMM's epilogue emit ``lo.forward(out)``."""
+    if lo is None:
         return {}
     return {"proj_w": lo.A32s, "proj_rows": lo.rows, "proj_p": lo.p if training else 0.0, "proj_seed": seed}
 
@@ -94,9 +87,8 @@ def _epi_proj_kw(lo, seed, training):
 def _epi_dt_kw(lo):
     """gemm kwargs that make a dgrad GEMM's epilogue emit the adapter's backward projection
     dT = dt_alpha·out·Bᵀ of its own output (the gradient entering ``lo``'s linear) — e.g. fc2's dgrad
-    producing fc1's dz and its dT in one pass instead of a lora_proj re-reading dz (MIFT_EPI_DT=0, read
-    per call: the separate pass)."""
-    if lo is None or os.environ.get("MIFT_EPI_DT", "1") == "0":
+    producing fc1's dz and its dT in one pass instead of a lora_proj re-reading dz."""
+    if lo is None:
         return {}
     return {"proj_w": lo.B32t, "proj_rows": lo.rows, "proj_alpha": lo.dt_alpha}
 
@@ -170,15 +162,13 @@ class _WgradBatch:
         self.cb = False
         if self.xs:
             self.flush()
-            join_side()
 
     def flush(self):
         if not self.xs:
             return
         arena, xs, ys, meta, ps, offs = self.arena, self.xs, self.ys, self.meta, self.ps, self.offs
         self.arena, self.xs, self.ys, self.meta, self.ps, self.offs = None, [], [], [], [], []
-        if not _diag_skip("wgrad"):
-            run_side(xs[0].device, lambda: K.lora_wgrad_group(arena.grad, xs, ys, meta, ps), *xs, *ys)
+        K.lora_wgrad_group(arena.grad, xs, ys, meta, ps)
         _notify(arena, offs)
 
 
@@ -493,12 +483,9 @@ def _ln_fold(ln, lin, w):
 
 
 def _gemm_ln(x2, ln, lin, w, act=0):
-    """Decode projection of LN(x): the folded form (K.gemm_ln_fold) unless MIFT_LN_FOLD=0 (read per call:
-    the LN-prologue form, K.gemm_ln).  Both are M <= 64 skinny-GEMM launches."""
-    if os.environ.get("MIFT_LN_FOLD", "1") != "0":
-        wf, c1, c2 = _ln_fold(ln, lin, w)
-        return K.gemm_ln_fold(x2, wf, c1, c2, ln.eps, act=act)
-    return K.gemm_ln(x2, ln.weight, ln.bias, ln.eps, w, lin.bias, act=act)
+    """Decode projection of LN(x): the folded form (K.gemm_ln_fold), one M <= 64 skinny-GEMM launch."""
+    wf, c1, c2 = _ln_fold(ln, lin, w)
+    return K.gemm_ln_fold(x2, wf, c1, c2, ln.eps, act=act)
 
 
 def ln_linear(x, ln, lin, lora_seed=0, training=True, link=None):
@@ -572,10 +559,10 @@ class MLP(torch.autograd.Function):
         # tile partials + one ordered reduction) instead of a lora_proj pass re-reading f
         pk = _epi_proj_kw(lo2, seed_l2, training)
         if act == 2:  # ReLU: relu'(z) = [f > 0], so f doubles as the backward's aux (no pre-activation store)
-            # ... or, 16x fewer bytes for the dgrad epilogue to read, the sign bits of f (MIFT_RELU_BITS=0: f)
+            # ... or, 16x fewer bytes for the dgrad epilogue to read, the sign bits of f (N1 % 8 != 0: f)
             N1 = fc1.w_nk().shape[0]
             bits = (torch.empty(h2.shape[0], N1 // 8, dtype=torch.uint8, device=h2.device)
-                    if N1 % 8 == 0 and os.environ.get("MIFT_RELU_BITS", "1") != "0" else None)
+                    if N1 % 8 == 0 else None)
             r = K.gemm(a, fc1.w_nk(), fc1.bias, T1, lo1.B32 if lo1 else None, act=act, sbits=bits, **pk)
             f, T2 = r if pk else (r, None)
             z = f if bits is None else bits
@@ -725,20 +712,11 @@ class LMHeadXentBlas(torch.autograd.Function):
         shp = h.shape
         h2 = _flat(h.contiguous())
         a, mean, rstd = K.layer_norm_fwd(h2, ln_w, ln_b, eps)
-        M = a.shape[0]
         lab = labels.reshape(-1)
-        chunk = _xent_chunk(M, w_nk.shape[0])
-        if chunk >= M:
-            logits = torch.matmul(a, w_nk.t())
-            loss_rows, _ = K.xent(logits, lab, V, ignore_index, write_grad=need_grad)
-        else:
-            logits = torch.empty(M, w_nk.shape[0], dtype=a.dtype, device=a.device)
-            loss_rows = torch.empty(M, dtype=torch.float32, device=a.device)
-            for r0 in range(0, M, chunk):
-                r1 = min(M, r0 + chunk)
-                lg = logits[r0:r1]
-                torch.matmul(a[r0:r1], w_nk.t(), out=lg)
-                loss_rows[r0:r1] = K.xent(lg, lab[r0:r1], V, ignore_index, write_grad=need_grad)[0]
+        # (row chunks of the logits GEMM measured slower, 6.10-6.38 vs 5.99 ms per distilgpt2 step, and saved
+        # no memory: the whole [M, V_pad] dlogits is kept for backward either way)
+        logits = torch.matmul(a, w_nk.t())
+        loss_rows, _ = K.xent(logits, lab, V, ignore_index, write_grad=need_grad)
         if need_grad:
             ctx.save_for_backward(h2, mean, rstd, ln_w, logits)
         ctx.shp, ctx.w_nk = shp, w_nk
@@ -800,18 +778,6 @@ def set_head_grad_mul(t):
 
 def head_grad_mul_used():
     return _HEAD_GMUL[1]
-
-
-def _xent_chunk(M, Vp):
-    """Rows per LM-head chunk (``MIFT_XENT_CHUNK``, default 0 = unchunked).
-
-    Measured on MI355X (distilgpt2, M = 8192, V_pad = 50304): chunks of 768 / 1024 / 2048 / 4096
-    rows ran 6.38 / 6.28 / 6.21 / 6.10 ms per step vs 5.99 unchunked — the smaller hipBLASLt GEMMs
-    lose more than the cache-resident xent pass gains, so chunking is opt-in (large-vocab,
-    memory-limited runs)."""
-    import os
-    c = int(os.environ.get("MIFT_XENT_CHUNK", "0"))
-    return M if c <= 0 or c >= M else c
 
 
 def lm_head_xent(h, ln, w_nk, labels, V, ignore_index=-100, need_grad=True, w_kn=None, shift=0):

@@ -83,9 +83,6 @@ class GradReducer:
             self._sync = old
 
     def _launch(self, b, where="finish"):
-        if where == "backward" and self.arena.grad.is_cuda:
-            from ..ops.streams import join
-            join()  # wgrad kernels queued on the side stream are ordered before the collective
         sl = self.arena.grad[b["lo"]:b["hi"]]
         maybe_inject(dist.get_rank(), self.step, "grads", grads=sl)
         with rng(f"mift.comm.bucket{b['idx']}.{where}"):

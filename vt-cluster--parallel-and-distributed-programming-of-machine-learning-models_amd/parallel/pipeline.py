@@ -766,7 +766,6 @@ class _StageGraphs:
         """Forward + backward graphs of one slot (private pool).  ``first``: no received activation
         (the embedding runs here); ``last``: the loss head runs here (seeded by ``self.gs``);
         ``pack``: this capture rebuilds the per-step LoRA operand packs (the step's first replay)."""
-        from ..ops import streams
         from ..ops.dispatch import C
         from ..ops.fused import invalidate_packs
         e = self.e
@@ -794,7 +793,6 @@ class _StageGraphs:
                     (y * self.gs).backward(retain_graph=True)
                 else:
                     torch.autograd.backward(y, grad_tensors=sl["g"], retain_graph=True)
-                streams.join()
         finally:
             if gc_was:
                 gc.enable()
@@ -804,19 +802,16 @@ class _StageGraphs:
 
     def _captured(self, body):
         from ..models.layers import graph_seeds
-        from ..ops import streams
         from ..ops.dispatch import C
         e = self.e
         torch.cuda.synchronize(e.device)
         gc.collect()
         torch.cuda.empty_cache()  # the eager warm-up's cached blocks: the slot pools are allocated next
         graph_seeds(True)
-        streams.set_enabled(False)
         try:
             return body()
         finally:
             graph_seeds(False)
-            streams.set_enabled(None)
             C().set_seed_step(None)
             e.stats["captures"] = e.stats.get("captures", 0) + 1
             torch.cuda.synchronize(e.device)

@@ -8,10 +8,10 @@ kernels get faster, with more micro-batches per step, and for small decode
 steps.  ``GraphedStep`` captures the forward and
 backward of all micro-batches of a step — LoRA packing, fused kernels, the
 hand-written fused LM head + cross-entropy — into ONE hipGraph and replays it: one host launch per
-step and no inter-kernel gaps.  ``MIFT_GRAPH_SIDE=1`` also forks the LoRA
-weight-gradient kernels onto a side stream inside the graph (mift.ops.streams);
-measured on MI355X it slows the co-running dgrad GEMMs more than it hides
-(device 6.18 vs 5.99 ms/step, tools/graph_overhead.py), so it is off.
+step and no inter-kernel gaps.  (Forking the LoRA weight-gradient kernels onto
+a side stream inside the graph slowed the co-running dgrad GEMMs more than it
+hid, device 6.18 vs 5.99 ms/step, and was removed: the graph has no parallel
+branches.)
 
 What stays outside the graph (per step, on the host stream):
   * staging the micro-batches into the graph's static input buffers
@@ -29,12 +29,10 @@ epoch gets its own graph or runs eagerly); the first step of every shape runs
 eagerly as warm-up (lazy library init, workspace allocation).
 """
 import gc
-import os
 
 import torch
 
 from ..models.layers import graph_seeds
-from ..ops import streams
 
 
 class GraphedStep:
@@ -95,7 +93,6 @@ class GraphedStep:
                     gscale = (tr.opt.loss_scale_t * ent["inv_ntok"]).reshape(())
                 seed = gscale
             loss_sum.backward(seed)
-            streams.join()
             acc = loss_sum.detach() if acc is None else acc + loss_sum.detach()
         C.set_seed_step(None)
         return acc
@@ -142,7 +139,6 @@ class GraphedStep:
         ms0 = model.micro_step
         torch.cuda.synchronize()
         graph_seeds(True)
-        streams.set_enabled(os.environ.get("MIFT_GRAPH_SIDE", "0") == "1")
         red = tr.reducer
         # no Python GC inside the capture: torch.cuda.graph collects once at entry, but a collection
         # triggered mid-capture ran finalizers of device objects and aborted the process (seen once
@@ -158,7 +154,6 @@ class GraphedStep:
             if gc_was:
                 gc.enable()
             graph_seeds(False)
-            streams.set_enabled(None)
             _C().set_seed_step(None)
             model.micro_step = ms0
         if self.pool is None:

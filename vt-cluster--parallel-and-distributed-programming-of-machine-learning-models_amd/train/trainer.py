@@ -166,8 +166,7 @@ class Trainer:
         model.micro_step = ms0
         g.seen.add(sig)
         g.prepare(mbs)
-        if os.environ.get("MIFT_DIAG_NOREBIND") != "1":
-            self.arena.rebind_grads()
+        self.arena.rebind_grads()
         self.arena.grad.zero_()
         if red is not None:
             red.begin_step()
