@@ -229,13 +229,24 @@ def test_interleaved_blocking_p2p_mode(single_drop):
 
 
 def test_chunk_slot_counts_cover_in_flight_micro_batches():
-    """Interleaved stage graphs: slot i % K_c of chunk c is free again (its backward queued) before
-    micro-batch i + K_c's receive is posted, for both receive policies."""
-    from mift.parallel.pipeline import chunk_slot_counts, schedule_interleaved
+    """Stage graphs and receive rings: slot i % K_c of chunk c is free again (its backward queued)
+    before micro-batch i + K_c's receive is posted, for both receive policies.  Plain 1F1B (V = 1)
+    keeps S - s + 1 slots whatever the micro-batch count and the policy."""
+    from mift.parallel.pipeline import recv_plan, schedule_interleaved, slot_counts
+    for S, M in [(2, 1), (2, 5), (4, 3), (4, 4), (4, 9), (8, 16)]:
+        for pre in (True, False):
+            for s in range(S):
+                assert slot_counts(S, s, M, 1, prefetch=pre) == [S - s + 1]
+                K, owner = S - s + 1, {}
+                for (op, _, i), recvs in zip(schedule_interleaved(S, s, M, 1), recv_plan(S, s, M, 1, pre)):
+                    for ii in [key[2] for key in recvs if key[0] == "F"] + ([i] if op == "F" else []):
+                        assert owner.setdefault(ii % K, ii) == ii, (S, M, s, ii)
+                    if op == "B":
+                        assert owner.pop(i % K) == i
     for S, V, M in [(2, 2, 2), (2, 2, 4), (4, 2, 8), (4, 4, 24), (8, 2, 16), (3, 3, 6)]:
         for pre in (True, False):
             for s in range(S):
-                K = chunk_slot_counts(S, s, M, V, prefetch=pre)
+                K = slot_counts(S, s, M, V, prefetch=pre)
                 ops = schedule_interleaved(S, s, M, V)
                 owner = [dict() for _ in range(V)]
                 for j, (op, c, i) in enumerate(ops):

@@ -38,12 +38,12 @@ design that also fixes its defects:
     receive buffer is safe to reuse once the compute that last read it has been queued — the
     rings below enforce exactly that order (``_Ring``: reuse of an unreleased slot raises);
   * hipGraph (GPU fused path, ``graph=True``): after one eager warm-up step per micro-batch
-    shape, each stage captures one forward graph and one backward graph per ring slot (slot =
-    micro-batch index mod (S - s + 1), the in-flight bound + the prefetched receive) and replays
-    them; p2p stays outside the graphs.  A slot's static output (y, or dX for the previous
-    stage) is rewritten by its next replay only after the compute stream waited for the send
-    that read it.  OPT-2.7B at the reference's micro-batch issues ~250 launches per micro-batch
-    from Python eagerly; a replay is one launch.
+    shape, each stage captures one forward graph and one backward graph per slot of every model
+    chunk it holds (slot = micro-batch index mod K_c, ``slot_counts``: the in-flight bound + the
+    prefetched receive, S - s + 1 for plain 1F1B) and replays them; p2p stays outside the graphs.
+    A slot's static output (y, or dX for the previous stage) is rewritten by its next replay only
+    after the compute stream waited for the send that read it.  OPT-2.7B at the reference's
+    micro-batch issues ~250 launches per micro-batch from Python eagerly; a replay is one launch.
 
 Interleaved 1F1B (``ctx.pp_virtual`` = V > 1, Narayanan et al. 2021 / Megatron-LM's
 interleaved schedule): the layers are split into S·V virtual stages and rank s holds chunks
@@ -56,10 +56,15 @@ leave the last rank for chunk c+1 on the first rank over a wrap-around pair of 2
 communicators (``ctx.wrap_f`` / ``ctx.wrap_b``); every communicator still carries one message
 kind between one sender and one receiver in an order both agree on (the k-th forward of every
 rank is the same (chunk, micro-batch), see ``schedule_interleaved``), receives are posted one op
-ahead into fresh buffers and waited right before their consumer, sends are asynchronous — a
-blocking-receive / async-send execution of this schedule is deadlock-free
-(tests/test_pipeline_cpu.py simulates it for every rank count tried).  The interleaved path runs
-eagerly (no stage graphs).
+ahead and waited right before their consumer, sends are asynchronous — a blocking-receive /
+async-send execution of this schedule is deadlock-free (tests/test_pipeline_cpu.py simulates it
+for every rank count tried).
+
+One scheduler runs both: plain 1F1B is the V = 1 case.  ``PipelineEngine.train_batch`` walks
+``schedule_interleaved(S, s, M, V)``, posts the receives ``recv_plan`` lists for each op (the two
+schedules prefetch differently, and that is the only place they differ) and hands each
+(chunk, micro-batch) to an eager (``_EagerRun``) or a replayed (``_GraphRun``) compute that owns
+the receive buffers.
 
 Loss normalisation: the last stage scales each micro-batch's summed token
 loss by ``loss_scale / global_ntokens`` (token-count normalisation over the
@@ -68,7 +73,6 @@ produce the same update for the same data.
 """
 import gc
 import os
-from collections import deque
 
 import torch
 
@@ -283,8 +287,7 @@ def schedule_interleaved(S, s, M, V):
 def simulate_schedule(S, M, V):
     """Execute every rank's op list with blocking receives and asynchronous sends; returns the
     number of ops run (== 2·S·M·V when the schedule cannot deadlock)."""
-    ops = [schedule_interleaved(S, s, M, V) if V > 1 else [(o, 0, i) for o, i in schedule_1f1b(S, s, M)]
-           for s in range(S)]
+    ops = [schedule_interleaved(S, s, M, V) for s in range(S)]
     done, pos, ran = set(), [0] * S, 0
     progress = True
     while progress:
@@ -304,6 +307,75 @@ def simulate_schedule(S, M, V):
                 ran += 1
                 progress = True
     return ran
+
+
+def recv_plan(S, s, M, V, prefetch=True):
+    """When rank s posts its receives: element j lists the ops of ``schedule_interleaved(S, s, M, V)``
+    whose input (the activation of an ('F', c, i), the gradient of a ('B', c, i)) is requested at the
+    top of op j, in posting order.  Every op that receives appears exactly once, at or before itself.
+
+    The position of a post among the compute launches decides what the transfer overlaps (RCCL makes
+    a p2p wait for the compute stream at post time), so the two schedules keep the policies they were
+    measured with.  Without ``prefetch`` (``MIFT_PP_P2P=blocking``, where a post also waits) every
+    receive is posted by its own consumer.  Plain 1F1B (V = 1) requests x(0) before the first op; a
+    forward F(i) requests the gradient of the steady-state backward that directly follows it, then
+    x(i+1); a cool-down backward requests its own gradient.  The interleaved schedule posts the
+    receive of op j if it is still missing, then that of op j+1."""
+    ops = schedule_interleaved(S, s, M, V)
+    nvs = S * V
+
+    def receives(op, c, i):
+        return c * S + s > 0 if op == "F" else c * S + s < nvs - 1
+
+    plan = [[] for _ in ops]
+    if not prefetch:
+        want = list(enumerate(ops))
+    elif V == 1:
+        nwarm = min(S - s - 1, M)
+        want = [(0, ("F", 0, 0))] if M else []
+        for j, (op, _, i) in enumerate(ops):
+            if op == "F":
+                if i >= nwarm:
+                    want.append((j, ("B", 0, i - nwarm)))
+                if i + 1 < M:
+                    want.append((j, ("F", 0, i + 1)))
+            elif i >= M - nwarm:
+                want.append((j, ("B", 0, i)))
+    else:
+        want = [(j, key) for j in range(len(ops)) for key in ops[j:j + 2]]
+    seen = set()
+    for j, key in want:
+        if receives(*key) and key not in seen:
+            seen.add(key)
+            plan[j].append(key)
+    return plan
+
+
+def slot_counts(S, s, M, V, prefetch=True):
+    """Receive-buffer / graph slots per model chunk on rank s: the most micro-batches of chunk c in
+    flight at once, from the post of the receive feeding F(c, i) (at the top of the op before it when
+    receives are prefetched; F itself on the first virtual stage, which receives nothing) until
+    B(c, i) has been queued.  Per chunk the forwards and the backwards both run in micro-batch order,
+    so the in-flight set is a run of consecutive micro-batches and slot i % K_c is never handed to
+    micro-batch i + K_c before B(c, i) — the condition RCCL needs for a receive into a reused buffer
+    (``_Ring``).  Plain 1F1B (V = 1) holds at most S - s micro-batches plus the prefetched one; it
+    keeps that count for every M and receive policy, so its captured graphs never depend on them."""
+    if V == 1:
+        return [S - s + 1]
+    ops = schedule_interleaved(S, s, M, V)
+    occ = [set() for _ in range(V)]
+    K = [1] * V
+    for j, (op, c, i) in enumerate(ops):
+        for jj in ((j, j + 1) if prefetch else (j,)):
+            if jj < len(ops) and ops[jj][0] == "F":
+                occ[ops[jj][1]].add(ops[jj][2])
+        for cc in range(V):
+            if occ[cc]:
+                assert max(occ[cc]) - min(occ[cc]) + 1 == len(occ[cc]), "in-flight set not consecutive"
+            K[cc] = max(K[cc], len(occ[cc]))
+        if op == "B":
+            occ[c].discard(i)
+    return K
 
 
 def head_cost_layers(cfg):
@@ -338,6 +410,7 @@ class PipelineEngine:
             raise ValueError(f"MIFT_PP_P2P={self.mode!r}: link | shared | blocking")
         self.blocking = self.mode == "blocking"
         self.V = getattr(ctx, "pp_virtual", 1) or 1
+        self.nvs = self.S * self.V  # virtual stages; chunk c of this rank is virtual stage c·S + s
         if self.V > 1:
             self.rx_wf, self.tx_wf = P2P(getattr(ctx, "wrap_f", None)), P2P(getattr(ctx, "wrap_f", None))
             self.rx_wb, self.tx_wb = P2P(getattr(ctx, "wrap_b", None)), P2P(getattr(ctx, "wrap_b", None))
@@ -348,11 +421,6 @@ class PipelineEngine:
         self.dtype, self.d = act_dtype, hidden_size
         self.device = ctx.device
         self.stats = {"fwd": 0, "bwd": 0, "replays": 0}
-        # receive rings: an activation lives until its micro-batch's backward (at most S - s in
-        # flight on stage s) plus the one prefetched ahead; a gradient only until its backward
-        self.K = self.S - self.s + 1
-        self._xring = _Ring(self.K, act_dtype, self.device, "activation")
-        self._gring = _Ring(2, act_dtype, self.device, "gradient")
         self.graphs = _StageGraphs(self) if graph else None
 
     # ---- per-micro-batch compute ----
@@ -370,13 +438,8 @@ class PipelineEngine:
         self.stats["fwd"] += 1
         return out["loss"].float() if head else out["hidden_states"]
 
-    def _backward(self, y, x, grad_y, gscale):
-        if self.last:
-            (y * gscale).backward()
-        else:
-            torch.autograd.backward(y, grad_tensors=grad_y)
-        self.stats["bwd"] += 1
-        return x.grad if x is not None else None
+    def _slot_counts(self, M):
+        return slot_counts(self.S, self.s, M, self.V, prefetch=not self.blocking)
 
     def _post(self, p2p, **kw):
         pend = p2p.post(**kw)
@@ -396,44 +459,23 @@ class PipelineEngine:
         and the gradient for the next backward before the forward that precedes it, each
         into a reusable ring buffer.  On RCCL ``Pending.wait()`` only orders the compute
         stream behind the transfer, so the host never blocks and xGMI transfers overlap the
-        forward / backward kernels."""
-        if self.V > 1:
-            run = self.graphs.runner(mbs, gscale, micro_step0) if self.graphs is not None else None
-            return self._schedule_interleaved(mbs, run or _EagerChunkRun(self, mbs, gscale, micro_step0))
-        if self.graphs is not None:
-            run = self.graphs.runner(mbs, gscale, micro_step0)
-            if run is not None:
-                return self._schedule(mbs, run)
-        return self._schedule(mbs, _EagerRun(self, mbs, gscale, micro_step0))
+        forward / backward kernels.
 
-    # ---- interleaved 1F1B (V model chunks per rank) ----
-    def _schedule_interleaved(self, mbs, run):
-        """Rank s's op list of ``schedule_interleaved``.  Receives are posted one op ahead of their
-        consumer (just in time under ``MIFT_PP_P2P=blocking``, whose ``_post`` waits on every receive:
-        a prefetch there would block on op j+1's input before op j's output is sent — with S = 2,
-        V = 2, M = 2 rank 0 would wait for the wrap-around activation of F(1, 0) before running F(0, 1),
-        which rank 1 needs first: ADVICE r4).  ``run`` is the eager (``_EagerChunkRun``) or the
-        replayed (``_ChunkGraphRun``) compute of one (chunk, micro-batch)."""
-        S, s, V, M = self.S, self.s, self.V, len(mbs)
-        ops = schedule_interleaved(S, s, M, V)
-        nvs = S * V
+        Rank s's op list of ``schedule_interleaved`` (V = 1: plain 1F1B), the receives of ``recv_plan``
+        posted at the top of each op: ahead of their consumer, or just in time under
+        ``MIFT_PP_P2P=blocking``, whose ``_post`` waits on every receive: a prefetch there would block
+        on op j+1's input before op j's output is sent — with S = 2, V = 2, M = 2 rank 0 would wait
+        for the wrap-around activation of F(1, 0) before running F(0, 1), which rank 1 needs first
+        (ADVICE r4).  ``run`` is the eager (``_EagerRun``) or the replayed (``_GraphRun``) compute of
+        one (chunk, micro-batch); it owns the receive buffers."""
+        run = self.graphs.runner(mbs, gscale, micro_step0) if self.graphs is not None else None
+        if run is None:
+            run = _EagerRun(self, mbs, gscale, micro_step0)
+        S, s, nvs = self.S, self.s, self.nvs
+        ops = schedule_interleaved(S, s, len(mbs), self.V)
+        plan = recv_plan(S, s, len(mbs), self.V, prefetch=not self.blocking)
         m = self.model
         posted, sends = {}, []
-        pre = not self.blocking
-
-        def vstage(c):
-            return c * S + s
-
-        def needs_recv(j):
-            if j >= len(ops):
-                return None
-            op, c, i = ops[j]
-            vs = vstage(c)
-            if op == "F" and vs > 0:
-                return op, c, i
-            if op == "B" and vs < nvs - 1:
-                return op, c, i
-            return None
 
         def post(key):
             op, c, i = key
@@ -446,22 +488,15 @@ class PipelineEngine:
             posted[key] = (self._post(p2p, recvs=[(buf, src)]), slot)
 
         def take(key):
-            if key not in posted:
-                post(key)
             pend, slot = posted.pop(key)
             pend.wait()
             return slot
 
         try:
-            for j, (op, c, i) in enumerate(ops):
-                key = needs_recv(j)
-                if key is not None and key not in posted:
+            for (op, c, i), recvs in zip(ops, plan):
+                for key in recvs:
                     post(key)
-                if pre:
-                    nxt = needs_recv(j + 1)  # one op of receive prefetch
-                    if nxt is not None and nxt not in posted:
-                        post(nxt)
-                vs = vstage(c)
+                vs = c * S + s
                 m.active_chunk = c
                 if op == "F":
                     xslot = take(("F", c, i)) if vs > 0 else None
@@ -484,204 +519,6 @@ class PipelineEngine:
             if p is not None:
                 p.wait()
         return run.finish()
-
-    def _schedule(self, mbs, run):
-        M = len(mbs)
-        nwarm = min(self.S - self.s - 1, M)
-        nsteady = M - nwarm
-        live = deque()
-        xq = deque()
-        sends = []
-        pre = not self.blocking  # prefetch receives ahead of the compute that needs them
-
-        def post_x(i):
-            if not self.first and i < M:
-                buf, slot = run.x_buffer(i)
-                xq.append((self._post(self.rx_f, recvs=[(buf, self.prev)]), slot))
-
-        def take_x(i):
-            if self.first:
-                return None, None
-            if not pre:
-                post_x(i)
-            pend, slot = xq.popleft()
-            pend.wait()
-            return run.x_input(i, slot), slot
-
-        def post_g(b):
-            if self.last:
-                return None
-            buf, slot = run.g_buffer(b)
-            return self._post(self.rx_b, recvs=[(buf, self.next)]), slot
-
-        def fwd(i, x):
-            y = run.forward(i, x)
-            if not self.last:
-                sends.append(run.send_y(i, self._post(self.tx_f, sends=[(y.detach(), self.next)])))
-            return y
-
-        def bwd(b, gp):
-            if gp is None and not pre:
-                gp = post_g(b)
-            bx, by, xslot = live.popleft()
-            g = None
-            if gp is not None:
-                pend, gslot = gp
-                pend.wait()
-                g = run.g_input(b, gslot)
-            gx = run.backward(b, by, bx, g)
-            if gp is not None:
-                run.release_g(gslot)
-            if not self.first:
-                sends.append(run.send_gx(b, self._post(self.tx_b, sends=[(gx, self.prev)])))
-            run.release_x(b, bx, xslot)
-
-        if pre:
-            post_x(0)
-        for i in range(nwarm):
-            x, xs = take_x(i)
-            if pre:
-                post_x(i + 1)
-            live.append((x, fwd(i, x), xs))
-        for j in range(nsteady):
-            i = nwarm + j
-            gp = post_g(j) if pre else None  # grad of the oldest live micro-batch, requested before the forward
-            x, xs = take_x(i)
-            if pre:
-                post_x(i + 1)
-            live.append((x, fwd(i, x), xs))
-            bwd(j, gp)
-        for k in range(nwarm):
-            b = nsteady + k
-            bwd(b, post_g(b) if pre else None)
-        for p in sends:
-            if p is not None:
-                p.wait()
-        return run.finish()
-
-
-class _EagerRun:
-    """Eager per-micro-batch compute of one ``train_batch`` (autograd builds a fresh graph per
-    micro-batch; receive buffers come from the engine's rings)."""
-
-    def __init__(self, eng, mbs, gscale, micro_step0):
-        self.e, self.mbs, self.gscale, self.ms0 = eng, mbs, gscale, micro_step0
-        self.loss = torch.zeros((), dtype=torch.float32, device=eng.device) if eng.last else None
-
-    def x_buffer(self, i):
-        return self.e._xring.get(self.e._act_shape(self.mbs[i]))
-
-    def x_input(self, i, slot):
-        return self.e._xring.buf(slot).requires_grad_(True)
-
-    def g_buffer(self, b):
-        return self.e._gring.get(self.e._act_shape(self.mbs[b]))
-
-    def g_input(self, b, slot):
-        return self.e._gring.buf(slot)
-
-    def forward(self, i, x):
-        y = self.e._forward(self.mbs[i], x, self.ms0 + i)
-        if self.e.last:
-            self.loss.add_(y.detach())
-        return y
-
-    def backward(self, b, y, x, g):
-        return self.e._backward(y, x, g, self.gscale)
-
-    def send_y(self, i, pend):
-        return pend
-
-    def send_gx(self, b, pend):
-        return pend
-
-    def release_x(self, b, x, slot):
-        if x is not None:
-            x.grad = None  # the ring slot is reused by a later micro-batch
-        if slot is not None:
-            self.e._xring.release(slot)
-
-    def release_g(self, slot):
-        self.e._gring.release(slot)
-
-    def finish(self):
-        return self.loss
-
-
-class _EagerChunkRun:
-    """Eager compute of one interleaved ``train_batch``: a fresh receive buffer per message (the
-    interleaved in-flight set has no ring bound to check), autograd graphs kept per (chunk, micro-batch)."""
-
-    def __init__(self, eng, mbs, gscale, micro_step0):
-        self.e, self.mbs, self.gscale, self.ms0 = eng, mbs, gscale, micro_step0
-        self.nvs = eng.S * eng.V
-        self.loss = torch.zeros((), dtype=torch.float32, device=eng.device) if eng.last else None
-        self.live = {}
-
-    def _last(self, c):
-        return c * self.e.S + self.e.s == self.nvs - 1
-
-    def x_buffer(self, c, i):
-        buf = torch.empty(self.e._act_shape(self.mbs[i]), dtype=self.e.dtype, device=self.e.device)
-        return buf, buf
-
-    g_buffer = x_buffer
-
-    def forward(self, c, i, x):
-        if x is not None:
-            x = x.requires_grad_(True)
-        y = self.e._forward(self.mbs[i], x, self.ms0 + i)
-        if self._last(c):
-            self.loss.add_(y.detach())
-        self.live[(c, i)] = (x, y)
-        return y
-
-    def backward(self, c, i, g):
-        x, y = self.live.pop((c, i))
-        if self._last(c):
-            (y * self.gscale).backward()
-        else:
-            torch.autograd.backward(y, grad_tensors=g)
-        self.e.stats["bwd"] += 1
-        return x.grad if x is not None else None
-
-    def send_y(self, c, i, pend):
-        return pend
-
-    send_gx = send_y
-
-    def release_x(self, c, i):
-        pass
-
-    def release_g(self, c, i, slot):
-        pass
-
-    def finish(self):
-        return self.loss
-
-
-def chunk_slot_counts(S, s, M, V, prefetch=True):
-    """Graph slots per model chunk on rank s of the interleaved schedule: the most micro-batches of
-    chunk c in flight at once, from the post of the receive feeding F(c, i) (at the top of the op
-    before it when receives are prefetched; F itself on the first virtual stage, which receives
-    nothing) until B(c, i) has been queued.  Per chunk the forwards and the backwards both run in
-    micro-batch order, so the in-flight set is a run of consecutive micro-batches and slot i % K_c is
-    never handed to micro-batch i + K_c before B(c, i) — the condition RCCL needs for a receive into
-    a reused buffer (``_Ring``)."""
-    ops = schedule_interleaved(S, s, M, V)
-    occ = [set() for _ in range(V)]
-    K = [1] * V
-    for j, (op, c, i) in enumerate(ops):
-        for jj in ((j, j + 1) if prefetch else (j,)):
-            if jj < len(ops) and ops[jj][0] == "F":
-                occ[ops[jj][1]].add(ops[jj][2])
-        for cc in range(V):
-            if occ[cc]:
-                assert max(occ[cc]) - min(occ[cc]) + 1 == len(occ[cc]), "in-flight set not consecutive"
-            K[cc] = max(K[cc], len(occ[cc]))
-        if op == "B":
-            occ[c].discard(i)
-    return K
 
 
 class _Ring:
@@ -717,10 +554,67 @@ class _Ring:
         self.busy[slot] = False
 
 
+class _EagerRun:
+    """Eager compute of one ``train_batch``: autograd builds a fresh graph per (chunk, micro-batch),
+    kept in ``live`` until its backward.  Receive buffers come from rings per chunk: an activation
+    lives until its micro-batch's backward (``slot_counts``), a gradient only until its own backward
+    was queued (2: the one being read and the one prefetched)."""
+
+    def __init__(self, eng, mbs, gscale, micro_step0):
+        self.e, self.mbs, self.gscale, self.ms0 = eng, mbs, gscale, micro_step0
+        self.loss = torch.zeros((), dtype=torch.float32, device=eng.device) if eng.last else None
+        self.xrings = [_Ring(k, eng.dtype, eng.device, "activation") for k in eng._slot_counts(len(mbs))]
+        self.grings = [_Ring(2, eng.dtype, eng.device, "gradient") for _ in self.xrings]
+        self.live = {}
+
+    def _last(self, c):
+        return c * self.e.S + self.e.s == self.e.nvs - 1
+
+    def x_buffer(self, c, i):
+        return self.xrings[c].get(self.e._act_shape(self.mbs[i]))
+
+    def g_buffer(self, c, i):
+        return self.grings[c].get(self.e._act_shape(self.mbs[i]))
+
+    def forward(self, c, i, xslot):
+        x = self.xrings[c].buf(xslot).requires_grad_(True) if xslot is not None else None
+        y = self.e._forward(self.mbs[i], x, self.ms0 + i)
+        if self._last(c):
+            self.loss.add_(y.detach())
+        self.live[(c, i)] = (x, y, xslot)
+        return y
+
+    def backward(self, c, i, gslot):
+        x, y, _ = self.live[(c, i)]
+        if self._last(c):
+            (y * self.gscale).backward()
+        else:
+            torch.autograd.backward(y, grad_tensors=self.grings[c].buf(gslot))
+        self.e.stats["bwd"] += 1
+        return x.grad if x is not None else None
+
+    def send_y(self, c, i, pend):
+        return pend
+
+    send_gx = send_y
+
+    def release_x(self, c, i):
+        x, _, xslot = self.live.pop((c, i))
+        if xslot is not None:
+            x.grad = None  # sent; the ring slot goes to a later micro-batch
+            self.xrings[c].release(xslot)
+
+    def release_g(self, c, i, slot):
+        self.grings[c].release(slot)
+
+    def finish(self):
+        return self.loss
+
+
 class _StageGraphs:
     """Per-slot forward / backward hipGraphs of one pipeline stage (see the module docstring).
 
-    Slot k serves micro-batches i with i % K == k (K = S - s + 1).  Its static buffers: the
+    Slot k of chunk c serves micro-batches i with i % K_c == k (``slot_counts``).  Its static buffers: the
     micro-batch inputs, the received activation x_k (a leaf that requires grad), the micro-step
     counter read by every dropout kernel (csrc/common.h ``mift_seed``), the forward output y_k
     (held with its autograd graph: the saved activations stay allocated), the received gradient
@@ -755,11 +649,8 @@ class _StageGraphs:
                 return None  # eager warm-up step for this shape; capture on the next one
             while len(self.sets) >= self.max_sets:
                 self.sets.popitem(last=False)  # least recently used signature
-            slots = self._capture(mbs) if self.e.V == 1 else self._capture_chunks(mbs)
-            self.sets[sig] = slots
+            slots = self.sets[sig] = self._capture(mbs)
         self.sets.move_to_end(sig)
-        if self.e.V > 1:
-            return _ChunkGraphRun(self, slots, mbs, gscale, micro_step0)
         return _GraphRun(self, slots, mbs, gscale, micro_step0)
 
     def _capture_slot(self, mbs, first, last, pack):
@@ -800,154 +691,45 @@ class _StageGraphs:
         sl.update(gf=gf, gb=gb, y=y, gx=(sl["x"].grad if not first else None))
         return sl
 
-    def _captured(self, body):
+    def _capture(self, mbs):
+        """``slots[c][k]`` for every chunk c of this rank and k < K_c (``slot_counts``), each with its
+        own pool.  Every rank's first op is F(0, 0), so slot (0, 0)'s forward carries the LoRA
+        operand packs; chunk c's multi-adapter packs are rebuilt inside its slot 0 (its first replay
+        of every step), which the chunk's later slots then read."""
         from ..models.layers import graph_seeds
         from ..ops.dispatch import C
         e = self.e
+        Ks = e._slot_counts(len(mbs))
         torch.cuda.synchronize(e.device)
         gc.collect()
         torch.cuda.empty_cache()  # the eager warm-up's cached blocks: the slot pools are allocated next
         graph_seeds(True)
         try:
-            return body()
+            slots = []
+            for c in range(e.V):
+                vs = c * e.S + e.s
+                e.model.active_chunk = c
+                slots.append([self._capture_slot(mbs, vs == 0, vs == e.nvs - 1, pack=(c == 0 and k == 0))
+                              for k in range(Ks[c])])
+            e.stats["fwd"] -= sum(Ks)  # the captures ran _forward once per slot
+            return slots
         finally:
+            e.model.active_chunk = None
             graph_seeds(False)
             C().set_seed_step(None)
             e.stats["captures"] = e.stats.get("captures", 0) + 1
             torch.cuda.synchronize(e.device)
 
-    def _capture(self, mbs):
-        e = self.e
-
-        def body():
-            # the per-step LoRA operand pack is captured into slot 0's forward (the step's first replay)
-            slots = [self._capture_slot(mbs, e.first, e.last, pack=(k == 0)) for k in range(e.K)]
-            e.stats["fwd"] -= e.K  # the captures ran _forward once per slot (backward bypassed _backward)
-            return slots
-
-        return self._captured(body)
-
-    def _capture_chunks(self, mbs):
-        """Interleaved schedule: slots per (chunk, micro-batch mod K_c) (``chunk_slot_counts``), each
-        with its own pool.  Every rank's first op is F(0, 0), so slot (0, 0)'s forward carries the LoRA
-        operand packs; chunk c's multi-adapter packs are rebuilt inside its slot 0 (its first replay
-        of every step), which the chunk's later slots then read."""
-        e = self.e
-        Ks = chunk_slot_counts(e.S, e.s, len(mbs), e.V, prefetch=not e.blocking)
-        nvs = e.S * e.V
-
-        def body():
-            slots = []
-            try:
-                for c in range(e.V):
-                    vs = c * e.S + e.s
-                    e.model.active_chunk = c
-                    slots.append([self._capture_slot(mbs, vs == 0, vs == nvs - 1, pack=(c == 0 and k == 0))
-                                  for k in range(Ks[c])])
-            finally:
-                e.model.active_chunk = None
-            e.stats["fwd"] -= sum(Ks)
-            return slots
-
-        return self._captured(body)
-
 
 class _GraphRun:
-    """Replay-based per-micro-batch compute of one ``train_batch`` (slot = i mod K)."""
-
-    def __init__(self, gr, slots, mbs, gscale, micro_step0):
-        self.gr, self.e, self.mbs, self.ms0 = gr, gr.e, mbs, micro_step0
-        self.slots = slots
-        self.K = gr.e.K
-        gr.gs.copy_(gscale.reshape(()))
-        self.steps = torch.arange(micro_step0, micro_step0 + len(mbs), dtype=torch.int64).to(
-            self.e.device, non_blocking=True)
-        self.loss = torch.zeros((), dtype=torch.float32, device=self.e.device) if self.e.last else None
-        self.xbusy = [False] * self.K
-        self.gbusy = [False] * self.K
-
-    def _slot(self, i):
-        return self.slots[i % self.K]
-
-    def x_buffer(self, i):
-        k = i % self.K
-        if self.xbusy[k]:
-            raise RuntimeError(f"pipeline activation slot {k} reused before its backward was queued")
-        self.xbusy[k] = True
-        return self._slot(i)["x"].detach(), k
-
-    def x_input(self, i, slot):
-        return self._slot(i)["x"]
-
-    def g_buffer(self, b):
-        k = b % self.K
-        if self.gbusy[k]:
-            raise RuntimeError(f"pipeline gradient slot {k} reused before its backward was queued")
-        self.gbusy[k] = True
-        return self._slot(b)["g"], k
-
-    def g_input(self, b, slot):
-        return self._slot(b)["g"]
-
-    def forward(self, i, x):
-        sl = self._slot(i)
-        if sl["send_y"] is not None:
-            sl["send_y"].wait()  # y_k of micro-batch i - K has left before the replay rewrites it
-            sl["send_y"] = None
-        for key, v in self.mbs[i].items():
-            sl["inp"][key].copy_(v, non_blocking=True)
-        sl["step"].copy_(self.steps[i:i + 1])
-        sl["gf"].replay()
-        self.e.stats["replays"] += 1
-        self.e.stats["fwd"] += 1
-        if self.e.last:
-            self.loss.add_(sl["y"].detach())
-        return sl["y"]
-
-    def backward(self, b, y, x, g):
-        sl = self._slot(b)
-        if sl["send_gx"] is not None:
-            sl["send_gx"].wait()
-            sl["send_gx"] = None
-        sl["gb"].replay()
-        self.e.stats["replays"] += 1
-        self.e.stats["bwd"] += 1
-        return sl["gx"]
-
-    def send_y(self, i, pend):
-        self._slot(i)["send_y"] = pend
-        return None  # waited per slot (and at the end of the step via finish)
-
-    def send_gx(self, b, pend):
-        self._slot(b)["send_gx"] = pend
-        return None
-
-    def release_x(self, b, x, slot):
-        if slot is not None:
-            self.xbusy[slot] = False
-
-    def release_g(self, slot):
-        self.gbusy[slot] = False
-
-    def finish(self):
-        for sl in self.slots:  # every send of this step has completed before the optimizer step
-            for key in ("send_y", "send_gx"):
-                if sl[key] is not None:
-                    sl[key].wait()
-                    sl[key] = None
-        return self.loss
-
-
-class _ChunkGraphRun:
-    """Replay-based compute of one interleaved ``train_batch``: micro-batch i of chunk c replays
-    slot (c, i mod K_c); a slot's static output (y, or dX) is rewritten only after the send that
-    read it completed, a slot is handed to a new micro-batch only after the old one's backward was
-    queued (raises otherwise)."""
+    """Replay-based compute of one ``train_batch``: micro-batch i of chunk c replays slot
+    (c, i mod K_c); a slot's static output (y, or dX) is rewritten only after the send that read it
+    completed, a slot is handed to a new micro-batch only after the old one's backward was queued
+    (raises otherwise)."""
 
     def __init__(self, gr, slots, mbs, gscale, micro_step0):
         self.gr, self.e, self.mbs = gr, gr.e, mbs
         self.slots = slots
-        self.nvs = self.e.S * self.e.V
         gr.gs.copy_(gscale.reshape(()))
         self.steps = torch.arange(micro_step0, micro_step0 + len(mbs), dtype=torch.int64).to(
             self.e.device, non_blocking=True)
@@ -983,7 +765,7 @@ class _ChunkGraphRun:
         sl["gf"].replay()
         self.e.stats["replays"] += 1
         self.e.stats["fwd"] += 1
-        if c * self.e.S + self.e.s == self.nvs - 1:
+        if c * self.e.S + self.e.s == self.e.nvs - 1:
             self.loss.add_(sl["y"].detach())
         return sl["y"]
 

@@ -140,12 +140,10 @@ def act_bytes_per_token_layer(cfg, dtype_bytes=2):
 
 def graph_slots(stages, micro_batches, virtual, rank=0):
     """Chunk-micro-batches of saved activations one captured stage-graph set holds on ``rank``: the
-    per-slot graphs of parallel/pipeline.py (K = S − s + 1 slots for 1F1B, Σ_c K_c for the
-    interleaved schedule), each keeping one forward's activations in its private pool."""
-    if virtual <= 1:
-        return stages - rank + 1
-    from .pipeline import chunk_slot_counts
-    return sum(chunk_slot_counts(stages, rank, micro_batches, virtual))
+    per-slot graphs of parallel/pipeline.py (Σ_c K_c, ``slot_counts``; K = S − s + 1 for plain
+    1F1B), each keeping one forward's activations in its private pool."""
+    from .pipeline import slot_counts
+    return sum(slot_counts(stages, rank, micro_batches, virtual))
 
 
 def choose_micro_batch(cfg, seq, per_replica, stages, dtype_bytes=2, hbm_bytes=288 * 10 ** 9,
